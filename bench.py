@@ -159,6 +159,33 @@ def impose_row_debt(opt, tokens_per_step, seed=0):
     return {"p_row_visited_per_step": round(p, 6), "mean_owed_steps": round(float(j.float().mean()), 2), "horizon": horizon}
 
 
+DUMP_PARAM_SAMPLE = 8 << 20     # parameters in the sample of the arena (32 MB of float32)
+DUMP_SEED = 20220711
+
+
+def dump_outputs(out_dir, tg, opt, last_losses):
+    """What the last timed step handed its caller, as float32 .npy files: the loss of each of its micro-batches, the emissions of
+    the last micro-batch, the head (linear + transitions) whole and a fixed seeded sample of the updated fp32 parameter arena (the
+    same indices in every run with the same arguments).  Lazy embedding rows are brought up to date first, as any reader of the
+    parameters does.  Untimed: runs after the timed region."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    a = tg.arena
+    opt.materialize()
+    torch.cuda.synchronize()
+    arrays = {"loss": torch.stack([l.reshape(()) for l in last_losses]),
+              "emissions": tg.last_emissions,
+              "grad_norm_sq": opt.norm_sq,
+              "linear_weight": a.param("linear.weight"), "linear_bias": a.param("linear.bias"),
+              "transitions": a.param("transitions")}
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, a.n, size=min(DUMP_PARAM_SAMPLE, a.n), dtype=np.int64))
+    arrays["params_sample"] = a.p.index_select(0, torch.from_numpy(idx).to(a.p.device))
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -194,6 +221,9 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="train with this dropout probability at the encoder's three HF sites + WordDropout (default 0: "
                          "BASELINE.md's workload is 'dropout off', and so is the cpu_baseline leg)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32, < 64 MB in all): the "
+                         "loss, the emissions, the head parameters, a fixed seeded sample of every updated parameter")
     ap.add_argument("--launch-check", action="store_true",
                     help="only check the launch: every rank joins a gloo group on the CPU, all-reduces its rank and rank 0 prints "
                          "{launch_check, world, ranks_seen}; no GPU work (tests/test_bench_launch_cpu.py)")
@@ -382,6 +412,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tg, opt, losses[-accum:])
     sentences = world * B * accum * args.steps
     value = sentences / dt
     loss_first, loss_last = float(losses[0]), float(losses[-1])
