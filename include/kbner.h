@@ -255,11 +255,11 @@ int kbner_colsum_rows_f32_batched(const long long* items, int n, int N, void* st
 int kbner_gemm_bf16_grouped_dyn(int layout, int nprob, const kbner_gemm_problem* probs, int* sched, void* stream);
 /* Which main loops the static launches of the three calls above use (process-wide, atomic; the A/B switch of tools/gemm_pp_lab.py,
  * tools/ab_step.sh, tools/wgrad_lab.py and of tests).  A bit field, default 3; bit-identical outputs in every setting (same MFMA
- * order per accumulator, same epilogue arithmetic):
+ * order per accumulator, same epilogue arithmetic).  A bit without a meaning in the build at hand is rejected with -22:
  *   bit 0  the ring kernels: 256-row tiles on the interleaved ring loop (gemm256f_kernel, round 4: 3 + 2 operand slots, every
  *          fragment read / LDS-DMA piece / cursor operation between two MFMAs), 128-row tiles on the same schedule with three
- *          48-KiB stages and one tile per workgroup (gemm128i_kernel, round 6; see bit 6).  Clear = the two-stage loop of rounds
- *          1-3 for both tile heights and for every dynamic launch.
+ *          48-KiB stages and one tile per workgroup (gemm128i_kernel, round 6).  Clear = the two-stage loop of rounds 1-3 for both
+ *          tile heights; dynamic launches with a K loop shorter than 16 steps run it in either setting.
  *   bit 1  ring, long-K launches (every K >= 16384, at least two tiles per CU -- the grouped weight gradients): the workgroups of
  *          an XCD meet between tiles so that the sharers of an operand panel stay within what their L2 holds (round 5: L2 misses
  *          of that launch 18.5 -> 13.9 GB, -0.5 ms per step).  Assumes the 32 workgroups with equal blockIdx & 7 are co-resident
@@ -267,20 +267,8 @@ int kbner_gemm_bf16_grouped_dyn(int layout, int nprob, const kbner_gemm_problem*
  *          stream's kernel -- a meeting times out (bounded, ~0.2 ms per tile boundary; correctness never depends on a meeting).
  *          Dynamic launches (the ones that share CUs with a collective) never meet.
  *   bit 2  + a meeting every 256 K steps inside a tile (11.25 GB = the two-stage loop's traffic exactly; no faster in the step).
- *   bit 3  128-row tiles on the two-stage loop although bit 0 is set (the deep ring's A/B).
- *   bit 4  (round 6, NOT default) a single K = 1024 forward problem with the bias + GELU + GELU' epilogue and at least two 128 x 256
- *          tiles per CU runs on csrc/gemm128x.hip: half-height tiles whose epilogue is spread over the NEXT tile's 16 K steps (the
- *          previous tile's 64 accumulators stay alive beside the current ones).  Bit-identical; measured SLOWER than the 256-row
- *          ring kernel on MI355X (1290-1340 against 1150-1225 us at 256 sentences: profiles/round6_gemm128x_lab.txt), kept as the
- *          A/B it is.
- *   bit 5  (round 6, NOT default) the same launches on csrc/gemm128s.hip: 128 x 256 tiles with WAVE-SPECIALISED epilogues (four MFMA
- *          waves hand the finished tile to four epilogue waves as bf16 through LDS; the pre-activation is rounded to bf16 before GELU, so
- *          results agree with the other kernels to one rounding, not bit for bit).  Also slower on MI355X (1271-1280 us): the loop is
- *          bound by the CU's vector-memory path, which the 128-row tile loads with 1.5 x the operand bytes.
- *   bit 6  128-row tiles on round 5's deep ring (gemm128r_kernel: 4 + 3 slots, A three K steps ahead, plain wait - barrier - burst -
- *          compute loop) instead of gemm128i_kernel: the A/B of the small-batch regime (4 sentences per step: 24.2 / 25.0 against
- *          25.1 / 25.7 us per 256-tile launch inside the step, 14.7 against 17.1 us for the 64-tile o-projection alone).
- *   bits 8-11  lab builds of gemm128x.hip / gemm128s.hip only (-DX128_LAB).  bits 12-15  trace builds only.
+ *   bits 12-15  trace builds only (-DG2_TRACE).  Kernels that lost their A/B live in tools/experiments/ and have bits of their
+ *   own in a lab build only (README.md there).
  * kbner_gemm_get_variant returns the current value. */
 int kbner_gemm_set_variant(int variant);
 int kbner_gemm_get_variant(void);

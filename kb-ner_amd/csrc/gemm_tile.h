@@ -1,6 +1,5 @@
-// Shared pieces of the 256-column-tile bf16 MFMA GEMM kernels (gemm256.hip: 256 x 256 tiles; gemm128x.hip: 128 x 256 tiles with
-// the previous tile's epilogue running under the current tile's K loop): problem descriptors, LDS-DMA issue helpers, LDS image
-// swizzles, the XCD-aware tile walk.  gfx950 only.
+// Shared pieces of the 256-column-tile bf16 MFMA GEMM kernels (gemm256.hip; the lab kernels of tools/experiments/): problem
+// descriptors, LDS-DMA issue helpers, LDS image swizzles, the XCD-aware tile walk.  gfx950 only.
 #pragma once
 #include "common.h"
 
@@ -308,10 +307,3 @@ static __device__ __forceinline__ void glds16_quad(const void* sbase, unsigned v
       : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(dst)
       : "memory", "m0");
 }
-
-// gemm128x.hip: 128 x 256 tiles, epilogue of tile i-1 under the K loop of tile i (K = 1024 problems only); returns 1 when the
-// launch is not one of its specialisations (the caller then takes the 256-row path), 0 / -hipError otherwise
-int kbner_launch128x(int layout, const GroupArgs& ga, hipStream_t stream);
-bool kbner_can128x(int layout, int M, int N, int K, int epi);
-// gemm128s.hip: the same tiles with wave-specialised epilogues (4 MFMA waves hand the tile to 4 epilogue waves through LDS)
-int kbner_launch128s(int layout, const GroupArgs& ga, hipStream_t stream);

@@ -13,8 +13,6 @@ Data layout in HBM (sized for 288 GB: everything stays resident, nothing is reco
 import logging
 import math
 
-import os
-
 import torch
 
 from . import lib as L_
@@ -289,13 +287,14 @@ class Tagger:
     Reference path: TransformerWordEmbeddings (flair/embeddings.py:2906) -> FastSequenceTagger.forward /
     forward_loss / _calculate_loss (flair/models/sequence_tagger_model.py:844,1899,2426)."""
 
-    def __init__(self, cfg, num_tags, start_idx, stop_idx, device="cuda", inference=False):
+    def __init__(self, cfg, num_tags, start_idx, stop_idx, device="cuda", inference=False, wgrad_overwrite=True, attn_residual=True):
         self.cfg, self.T, self.start, self.stop = cfg, num_tags, start_idx, stop_idx
         self.device = torch.device(device)
         self.arena = Arena(tagger_specs(cfg, num_tags), self.device, with_grad=not inference)
         # every weight gradient of the encoder is a tile of the grouped 256 x 256 launch (_wgrads): it may overwrite
         self.arena.wgrad_overwrite_ok = (not inference and cfg.hidden_size % 256 == 0 and cfg.intermediate_size % 256 == 0
-                                         and os.environ.get("KBNER_WGRAD_OVERWRITE", "1") != "0")   # (A/B switch: README "Switches")
+                                         and bool(wgrad_overwrite))   # (False: zero them every step, the round-5 A/B)
+        self.ATTN_RESIDUAL = bool(attn_residual)   # (False: D from the bf16 O alone, the round-3 backward; see the class default)
         self._acts = {}
         self._saved = None
         # Dropout (active only while `training`): the encoder's three HF sites (embeddings, attention probabilities,
@@ -391,8 +390,9 @@ class Tagger:
             self.arena.refresh_shadow()
 
     # the attention forward also keeps O - bf16(O) (one byte per element and layer) and the backward takes its softmax
-    # correction D from the pair: include/kbner.h kbner_attn_bwd.  KBNER_ATTN_RESIDUAL=0: D from the bf16 O alone (round 3).
-    ATTN_RESIDUAL = os.environ.get("KBNER_ATTN_RESIDUAL", "1") != "0"
+    # correction D from the pair: include/kbner.h kbner_attn_bwd.  Class default of the constructor's attn_residual; without it a query.weight
+    # gradient is 16 % off at L = 24, so tests/test_abi_cpu.py pins the default.
+    ATTN_RESIDUAL = True
     ACTS_BUDGET_BYTES = 120 << 30  # resident activation sets (one per (B, S) shape), least-recently-used first out
 
     def acts(self, B, S):
@@ -445,9 +445,9 @@ class Tagger:
     # host-bound on a slower one (the driver's round-3 box: 1154 instead of 2400-2700 sentences/s).  Nothing in such a pass
     # depends on the host (no dropout seeds, fixed shapes, buffers that live as long as the (B, S) activation set), so the third
     # pass over a shape is captured into a HIP graph and every later one is three small input copies + ONE graph launch.
-    # KBNER_INFER_GRAPH=0 keeps the eager launches (A/B).
-    INFER_GRAPH = os.environ.get("KBNER_INFER_GRAPH", "1") != "0"
-    INFER_GRAPH_DP = os.environ.get("KBNER_INFER_GRAPH_DP", "0") == "1"    # opt in on data-parallel ranks (untested over RCCL)
+    # Tagger.INFER_GRAPH = False keeps the eager launches (A/B).
+    INFER_GRAPH = True
+    INFER_GRAPH_DP = False    # opt in on data-parallel ranks (untested over RCCL)
 
     def encoder_forward(self, ids, pos_ids, maskbias, B, S, need_grad=True):
         if (need_grad or not self.INFER_GRAPH or self.training or ops.SCHED_RING is not None or ops.GEMM_HOOK is not None

@@ -48,6 +48,22 @@ def test_product_path_never_imports_oracle():
     assert not bad, bad
 
 
+def test_product_path_reads_no_environment_switch():
+    """kbner/engine.py and kbner/ops.py take their A/B switches as arguments and attributes, never from the environment, and the
+    defaults are pinned: without the attention residual a query.weight gradient is 16 % off."""
+    import inspect
+    import __graft_entry__ as ge
+    for f in ("engine.py", "ops.py"):
+        src = open(os.path.join(ge.PKG, "kbner", f)).read()
+        assert "environ" not in src and "getenv" not in src, f
+    from kbner import ops
+    from kbner.engine import Tagger
+    assert Tagger.ATTN_RESIDUAL is True and Tagger.INFER_GRAPH is True and Tagger.INFER_GRAPH_DP is False
+    assert ops.MIN_TILES_256 == 32
+    par = inspect.signature(Tagger.__init__).parameters
+    assert par["wgrad_overwrite"].default is True and par["attn_residual"].default is True
+
+
 def test_batch_assembly_matches_oracle_compaction():
     from kbner import batch as kb
     from oracle import crf as ocrf

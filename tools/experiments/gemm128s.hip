@@ -18,7 +18,7 @@
 // accumulator since round 4) -- results agree with the 256-row kernel to one bf16 rounding of the pre-activation, not bit for bit;
 // a two-stage operand ring (2 x 48 KiB: both operands ONE step ahead) because the hand-off buffer takes 64 of the 160 KiB.
 // One barrier per K step + one behind the hand-off, executed by all eight waves.
-#include "gemm_tile.h"
+#include "gemm128_lab.h"
 
 #define S_A_BYTES 16384
 #define S_STAGE (S_A_BYTES + TILE2_BYTES)     // 48 KiB: A tile (128 rows) + B tile (256 rows)

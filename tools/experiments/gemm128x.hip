@@ -1,7 +1,7 @@
 // bf16 MFMA GEMM, third structure (round 6): 128 x 256 x 64 tiles whose EPILOGUE RUNS UNDER THE NEXT TILE'S K LOOP.
 //
 // Why.  The encoder's three K = 1024 GEMMs with heavy epilogues -- FFN-up forward (bias + GELU + GELU'; HF BertIntermediate behind
-// /root/reference/flair/embeddings.py:3269), FFN-down dgrad (GELU' x dY + column sums), o-projection forward (bias + residual) --
+// flair/embeddings.py:3269 of the reference), FFN-down dgrad (GELU' x dY + column sums), o-projection forward (bias + residual) --
 // ran at 0.385 / 0.413 / 0.40 of the dense bf16 MFMA peak on the 256 x 256 ring kernel while every long-K shape ran at 0.50-0.55:
 // a 256 x 256 x 1024 tile is 16 K steps (~43.7 K shader cycles) followed by an epilogue during which the matrix pipe idles
 // (13.75 K cycles of erf arithmetic for GELU + GELU', two waves per SIMD serialised on the VALU port) and a store burst that
@@ -32,8 +32,8 @@
 // so that every accumulator index is static.
 //
 // Results are bit-identical to the 256-row kernels' (same MFMA order per output element, same epilogue arithmetic):
-// tests/test_gpu_kernels.py test_gemm128x_*.
-#include "gemm_tile.h"
+// tools/gemm128x_lab.py --skip-bench on a lab build (README.md here).
+#include "gemm128_lab.h"
 
 #define X_A_BYTES 16384
 #define X_B_BASE (3 * X_A_BYTES)

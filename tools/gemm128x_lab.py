@@ -1,7 +1,9 @@
 #!/usr/bin/env python
-"""Lab for csrc/gemm128x.hip (128 x 256 tiles, the previous tile's epilogue under the current tile's K loop; round 6).
+"""Lab for tools/experiments/gemm128x.hip and gemm128s.hip (128 x 256 tiles, the previous tile's epilogue under the current tile's K loop; round 6).
 For each case: the 256-row kernels (kbner_gemm_set_variant without bit 4) against the same launch with bit 4 set -- results must
 be EQUAL (same MFMA order per element, same epilogue arithmetic) -- then TFLOP/s of both, alternating.
+Needs the LAB build of the library (tools/experiments/README.md: -DKBNER_GEMM_LAB, selected with KBNER_LIB); the product library
+has neither kernel and rejects their variant bits, so the tool stops at once there.  --bit 0: the 256-row kernels alone.
     python tools/gemm128x_lab.py [--sentences 256] [--reps 20] [--skip-bench] [--cases ffn_up,oproj,ffn_down_dgrad,qkv]"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,11 +22,18 @@ ap.add_argument("--cases", default="ffn_up")
 ap.add_argument("--base", type=int, default=3, help="variant bits of the reference launch")
 ap.add_argument("--bit", type=int, default=16, help="variant bit of the kernel under test: 16 = gemm128x (bit-identical), 32 = gemm128s (wave-specialised epilogue: the pre-activation is rounded to bf16 before GELU, compared with a tolerance)")
 ap.add_argument("--tol", type=float, default=4e-3, help="--bit 32: relative-L2 tolerance of the outputs")
-ap.add_argument("--variants", default="", help="extra kbner_gemm_set_variant values to time next to --base (e.g. 35,67,99: phased start)")
+ap.add_argument("--variants", default="", help="extra kbner_gemm_set_variant values to time next to --base (e.g. 35)")
 ap.add_argument("--strace", default="", help="gemm128s lab trace ids (7 idle epilogue, 8 full): cycles of wave 0 per K step and around the hand-off")
 ap.add_argument("--trace", default="", help="lab library: ablation ids built with the cycle trace (11 full, 13 no stores, 14 neither): print per-segment cycles")
 ap.add_argument("--abl", default="", help="lab library (KBNER_LIB=kb-ner_amd/kbner/_exp/libkbner_lab.so): ablation ids 1-8 to time next to the full kernel")
 a = ap.parse_args()
+lab_bits = a.bit | (0xF00 if a.abl or a.trace or a.strace else 0) | (32 if a.strace else 0)
+_v0 = ops.gemm_variant()
+if lab_bits & ~7 and L.load().kbner_gemm_set_variant(_v0 | lab_bits) != 0:
+    sys.exit("tools/gemm128x_lab.py: this library has no variant bit %d%s -- build the lab library (tools/experiments/README.md: "
+             "-DKBNER_GEMM_LAB%s) and select it with KBNER_LIB" % (a.bit, " / bits 8-11" if lab_bits & 0xF00 else "",
+                                                                    " -DX128_LAB" if lab_bits & 0xF00 else ""))
+ops.gemm_variant(_v0)
 dev = "cuda"
 H, F, S = 1024, 4096, 512
 

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/gemm128x_pmc.sh <outdir> [abl ids]  -- L2 / fabric counters of the FFN-up forward GEMM on the
-# 256-row ring kernel and on gemm128x (lab library: -DX128_LAB build of csrc/gemm128x.hip, kb-ner_amd/kbner/_exp/libkbner_lab.so)
+# 256-row ring kernel and on gemm128x (lab library: the -DKBNER_GEMM_LAB -DX128_LAB build of tools/experiments/README.md,
+# kb-ner_amd/kbner/_exp/libkbner_lab.so; the tool refuses to run on the product library)
 out=${1:-gpurun_out/r6/x_pmc}
 abl=${2:-2,3}
 mkdir -p $out

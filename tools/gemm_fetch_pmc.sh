@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_READ_sum TCC_REQ_sum"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --kernel-trace --pmc $set -d $out/p$i --output-format csv -- python tools/gemm128x_lab.py --sentences 256 --reps 1 --cases ffn_up,qkv,oproj,ffn_down_dgrad > $out/p$i.log 2>&1 || echo "pass $i ($set) failed"
+  timeout 300 rocprofv3 --kernel-trace --pmc $set -d $out/p$i --output-format csv -- python tools/gemm128x_lab.py --bit 0 --sentences 256 --reps 1 --cases ffn_up,qkv,oproj,ffn_down_dgrad > $out/p$i.log 2>&1 || echo "pass $i ($set) failed"
 done
 python - <<PY
 import collections, csv, glob, os, re
@@ -22,7 +22,7 @@ for d in sorted(glob.glob(os.path.join(out, "p*"))):
             per[(int(r["Dispatch_Id"]), r["Counter_Name"])] += float(r["Counter_Value"])
         for (disp, c), v in per.items():
             rows[disp][c] = v
-# dispatch order of the lab: per case  [variant 3 check, (variant 19 falls back to the same kernel for non-GELU cases)], then timed launches
+# dispatch order of the lab: per case  [variant 3 check, twice (--bit 0)], then timed launches
 disps = sorted(rows)
 print("dispatch  FETCH_SIZE x2 [MB]  WRITE_SIZE [MB]  TCC_READ  TCC_MISS  (gemm256f launches in order: ffn_up, qkv, oproj, ffn_down_dgrad blocks)")
 for dsp in disps:

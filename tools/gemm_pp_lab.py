@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Round-4 A/B of the 256x256 GEMM main loops (kbner_gemm_set_variant): bit-identity of the ping-pong kernel against the two-stage
 kernel on every engine epilogue, then the engine-shaped per-layer mix at M tokens, each variant timed back to back in one process.
-  python tools/gemm_pp_lab.py [--M 65536] [--reps 10] [--variants 0,1,3,9,11]"""
+  python tools/gemm_pp_lab.py [--M 65536] [--reps 10] [--variants 0,1,3,7]"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "kb-ner_amd"))
@@ -17,7 +17,7 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--variants", default="0,1")
 ap.add_argument("--skip-check", action="store_true")
 ap.add_argument("--skip-bench", action="store_true")
-ap.add_argument("--kstep", default="", help="variants for the long-K per-step timing (may include the timing-only ablation bits 16 / 32)")
+ap.add_argument("--kstep", default="", help="variants for the long-K per-step timing (kbner_gemm_set_variant values)")
 a = ap.parse_args()
 variants = [int(v) for v in a.variants.split(",")]
 dev, BF = "cuda", torch.bfloat16

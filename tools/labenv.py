@@ -16,6 +16,7 @@ def apply():
         lib.LIB_PATH = p
     handle = lib.load()
     v = os.environ.get("KBNER_GEMM_VARIANT")
-    if v:
-        handle.kbner_gemm_set_variant(int(v))
+    if v and handle.kbner_gemm_set_variant(int(v)) != 0:
+        raise SystemExit("KBNER_GEMM_VARIANT=%s: this library build has no such variant bit (include/kbner.h; the lab bits need "
+                         "the lab build of tools/experiments/README.md, selected with KBNER_LIB)" % v)
     return handle
