@@ -1175,7 +1175,6 @@ static inline int pick_rpw(int B, int S, int A) {
   return rpw;
 }
 
-static int at_cu_count() { return kbner_cu_count(); }
 
 template <int NKB, bool DROP>
 static int launch_attn_fwd2(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, uint8_t* ctx_lo, float* lse, int B, int H, int A, int rpw,
@@ -1186,7 +1185,7 @@ static int launch_attn_fwd2(const bf16_t* qkv, const float* maskbias, bf16_t* ct
   r = kbner_set_max_lds_once(done1, reinterpret_cast<const void*>(attn_fwd_kernel<NKB, DROP, true>), AT_LDS_BYTES);
   if (r) return r;
   const int S = NKB * 16;
-  const int ncu = at_cu_count();
+  const int ncu = kbner_cu_count();
   // 32 rows per wave and pass (round 3): half the LDS bytes per flop.  Not with dropout: in halves the keep tests push the S = 512
   // instantiation over 256 VGPRs (94-148 spills), in quarters it fits but runs at 322 us against the 16-row kernel's 315
   if (rows32 && !DROP && NKB % 4 == 0 && rpw % 256 == 0) {
@@ -1310,7 +1309,7 @@ int kbner_attn_fwd(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, uint8_
   hipStream_t st = (hipStream_t)stream;
 #ifdef KBNER_ATTN_LAB
   // (the streaming kernel counts its own stores and does not write ctx_lo: with a residual requested the panel kernels run)
-  if (!ctx_lo && ((attn_variant() == 3 && S >= 256 && B * A >= at_cu_count()) || attn_variant() == 4))   // 4: forced (small cases)
+  if (!ctx_lo && ((attn_variant() == 3 && S >= 256 && B * A >= kbner_cu_count()) || attn_variant() == 4))   // 4: forced (small cases)
     return kbner_attn_fwd3(qkv, maskbias, ctx, lse, B, S, H, A, drop_seed, drop_thresh, st);
   const bool rows32 = attn_variant() != 1;
 #else

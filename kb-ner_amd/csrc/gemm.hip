@@ -19,14 +19,7 @@
 // Replaces the cuBLAS calls behind torch.nn.Linear / autograd in transformers' BertSelfAttention,
 // BertSelfOutput, BertIntermediate, BertOutput (reached from flair/embeddings.py:3269).
 #include "common.h"
-
-#define EPI_BIAS 1     // + bias[n]
-#define EPI_GELU 2     // C = gelu(pre), out2 = gelu'(pre) (bf16)
-#define EPI_ADD 4      // + addend[m,n] (bf16)
-#define EPI_GELU_FWD 1024  // C = gelu(pre) alone (inference)
-#define EPI_DGELU 8    // * aux[m,n]  (aux = the gelu'(pre) the forward epilogue stored)
-#define EPI_ATOMIC32 16  // atomicAdd into C32 (fp32), no bf16 output
-#define EPI_DROP 128     // dropout on (acc*alpha + bias) before the residual add
+#include "gemm_epi.h"
 
 struct GemmArgs {
   const bf16_t* A;

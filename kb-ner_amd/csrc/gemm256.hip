@@ -10,6 +10,7 @@
 // 32-byte-block XOR swizzle so ds_read_b64_tr_b16 is bank-conflict free (8 k-rows x 32 B per half-wave
 // land on 64 distinct banks).
 #include "gemm_tile.h"
+#include <type_traits>
 
 // Epilogue of one 256x256 tile, instantiated per flag set (EPI_CT; -1 = generic runtime flags for uncommon
 // combinations).  With runtime flags every (row-fragment, column-half) step is a chain of ~10 scalar branches and its
@@ -96,7 +97,7 @@ static __device__ __forceinline__ void epilogue256(const GemmProblem& g, f4v (&a
     drd1 = (unsigned)(r * 128 + (((1 * 4 + gq) ^ kc_swz(r)) << 4));
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      glds16_pair<0>(dsrc, dv0, dv1, ((f & 2) ? dbuf2 : dbuf) + (unsigned)(f & 1) * 2048u);
+      glds16_pair(dsrc, dv0, dv1, ((f & 2) ? dbuf2 : dbuf) + (unsigned)(f & 1) * 2048u);
       dsrc += dstep;
     }
   } else if (has_in) {
@@ -243,7 +244,7 @@ static __device__ __forceinline__ void epilogue256(const GemmProblem& g, f4v (&a
       // this fragment's buffer is done with (operand rows read, output rows staged and read back: the stores above carry them):
       // fragment mi + 4's operand rows go there
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      glds16_pair<0>(dsrc, dv0, dv1, ((mi & 2) ? dbuf2 : dbuf) + (unsigned)(mi & 1) * 2048u);
+      glds16_pair(dsrc, dv0, dv1, ((mi & 2) ? dbuf2 : dbuf) + (unsigned)(mi & 1) * 2048u);
       dsrc += dstep;
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -288,6 +289,54 @@ static __device__ __forceinline__ void epilogue256(const GemmProblem& g, f4v (&a
   // the specialised variants consume every load on straight-line code.
   if constexpr (EPI_CT < 0 && DRAIN) __builtin_amdgcn_s_waitcnt(0x0F70);
 }
+
+// Which epilogue256 instantiation a tile's run-time flags (`epi`) select: the table of specialised flag sets, once, for the three
+// kernels.  The kernel defines EPI_RUN(E) / EPI_RUN_GENERIC() as its epilogue256 call (they differ in MI, DRAIN, IN_DMA, scr2).
+// Forward (NT) tiles take the specialised epilogues; the dgrad layout (whose transpose-read B operand leaves fewer free registers)
+// only the plain / residual-add ones -- RING_DGRAD: the 256-row ring kernel also the FFN-down dgrad's x GELU' (+ column sums),
+// which the two-stage kernel keeps generic: specialised there it spilled and measured slower in situ than the generic epilogue.
+// EPI_STORE32: the weight gradients of the first backward pass after an optimizer step (overwrite).
+// (a macro: as a __forceinline__ function the same table compiles to the same instructions with one branch inverted)
+#define DISPATCH_EPILOGUE(A_KS, B_KS, RING_DGRAD) \
+  if (!B_KS) { \
+    switch (epi) { \
+      case 0: EPI_RUN(0); break; \
+      case EPI_BIAS: EPI_RUN(EPI_BIAS); break; \
+      case EPI_BIAS | EPI_GELU: EPI_RUN(EPI_BIAS | EPI_GELU); break; \
+      case EPI_BIAS | EPI_GELU_FWD: EPI_RUN(EPI_BIAS | EPI_GELU_FWD); break; \
+      case EPI_BIAS | EPI_ADD: EPI_RUN(EPI_BIAS | EPI_ADD); break; \
+      case EPI_BIAS | EPI_ADD | EPI_DROP: EPI_RUN(EPI_BIAS | EPI_ADD | EPI_DROP); break; \
+      default: EPI_RUN_GENERIC(); break; \
+    } \
+  } else if (A_KS && epi == EPI_RMW32) { \
+    EPI_RUN(EPI_RMW32); \
+  } else if (A_KS && epi == EPI_STORE32) { \
+    EPI_RUN(EPI_STORE32); \
+  } else if (!A_KS && epi == EPI_ADD) { \
+    EPI_RUN(EPI_ADD); \
+  } else if (!A_KS && epi == 0) { \
+    EPI_RUN(0); \
+  } else if (RING_DGRAD && !A_KS && epi == (EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS)) { \
+    EPI_RUN(EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS); \
+  } else if (RING_DGRAD && !A_KS && epi == EPI_DGELU) { \
+    EPI_RUN(EPI_DGELU); \
+  } else { \
+    EPI_RUN_GENERIC(); \
+  }
+
+// One 8-MFMA group of the ring kernels (A fragments a[0..1] x B fragments b[0..3] -> accumulator rows 2 pr, 2 pr + 1) with one filler
+// statement behind each MFMA, pinned by sched_barriers.  MF(a, b, mi, ni, Z) is the kernel's MFMA statement (Z: the MFMA starts its
+// accumulator).  #undef'ed at the end of the file.
+#define G8_SB() __builtin_amdgcn_sched_barrier(0)
+#define G8_GROUP(MF, Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) \
+  MF(a, b, 2 * (pr), 0, Z); G8_SB(); f0; G8_SB();                 \
+  MF(a, b, 2 * (pr), 1, Z); G8_SB(); f1; G8_SB();                 \
+  MF(a, b, 2 * (pr), 2, Z); G8_SB(); f2; G8_SB();                 \
+  MF(a, b, 2 * (pr), 3, Z); G8_SB(); f3; G8_SB();                 \
+  MF(a, b, 2 * (pr) + 1, 0, Z); G8_SB(); f4; G8_SB();             \
+  MF(a, b, 2 * (pr) + 1, 1, Z); G8_SB(); f5; G8_SB();             \
+  MF(a, b, 2 * (pr) + 1, 2, Z); G8_SB(); f6; G8_SB();             \
+  MF(a, b, 2 * (pr) + 1, 3, Z); G8_SB(); f7; G8_SB();
 
 // -DG2_TRACE (tools/gemm_trace.sh, never the product build): wave 0 stamps s_memtime at tile start / main-loop end /
 // epilogue end so tools/gemm_trace.py can split a persistent workgroup's time per tile.
@@ -475,30 +524,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GroupArgs ga) {
   }
   const int epi = g.epi;
   unsigned char* scr = smem + 2 * STAGE2_BYTES + wid * 4096;
-  // forward (NT) tiles take the specialised epilogues; the dgrad layout (whose transpose-read B operand leaves fewer free
-  // registers) only the plain / residual-add ones -- its specialised GELU' + column-sum variant spills and measured
-  // slower in situ than the generic epilogue
-  if (!B_KS) {
-    switch (epi) {
-      case 0: epilogue256<0, MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      case EPI_BIAS: epilogue256<EPI_BIAS, MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      case EPI_BIAS | EPI_GELU: epilogue256<(EPI_BIAS | EPI_GELU), MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      case EPI_BIAS | EPI_GELU_FWD: epilogue256<(EPI_BIAS | EPI_GELU_FWD), MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      case EPI_BIAS | EPI_ADD: epilogue256<(EPI_BIAS | EPI_ADD), MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      case EPI_BIAS | EPI_ADD | EPI_DROP: epilogue256<(EPI_BIAS | EPI_ADD | EPI_DROP), MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-      default: epilogue256<-1, MI>(g, acc, m0, n0, wm, wn, lane, scr); break;
-    }
-  } else if (A_KS && epi == EPI_RMW32) {
-    epilogue256<EPI_RMW32, MI>(g, acc, m0, n0, wm, wn, lane, scr);
-  } else if (A_KS && epi == EPI_STORE32) {
-    epilogue256<EPI_STORE32, MI>(g, acc, m0, n0, wm, wn, lane, scr);
-  } else if (!A_KS && epi == EPI_ADD) {
-    epilogue256<EPI_ADD, MI>(g, acc, m0, n0, wm, wn, lane, scr);
-  } else if (!A_KS && epi == 0) {
-    epilogue256<0, MI>(g, acc, m0, n0, wm, wn, lane, scr);
-  } else {
-    epilogue256<-1, MI>(g, acc, m0, n0, wm, wn, lane, scr);
-  }
+#define EPI_RUN(E) epilogue256<(E), MI>(g, acc, m0, n0, wm, wn, lane, scr)
+#define EPI_RUN_GENERIC() epilogue256<-1, MI>(g, acc, m0, n0, wm, wn, lane, scr)
+  DISPATCH_EPILOGUE(A_KS, B_KS, false)
+#undef EPI_RUN
+#undef EPI_RUN_GENERIC
   G2_T(2)
   ++tile_no;
   if (!has_next) { G2_CLK(1) break; }
@@ -670,102 +700,26 @@ __global__ __launch_bounds__(512, 2) void gemm256f_kernel(const GroupArgs ga) {
   unsigned sa_off = 0, sb_off = PP_B_BASE;
   int tile_no = 0;
   (void)tile_no;
-#define RF_SB() __builtin_amdgcn_sched_barrier(0)
+#define RF_SB() G8_SB()
 #define RF_NOP (void)0
   // Fragment addresses.  Row-major (KC) images: ONE address register per operand and k half for the whole step -- the row block
   // (A: mi * 2 KiB, B: (ni >> 1) * 4 KiB + (ni & 1) * 512 B) is the ds_read's immediate offset and k half 1 is k half 0 with
   // bit 6 flipped (the chunk swizzles only look at row bits the row block does not touch) -- made opaque so that hipcc keeps this
   // form (left alone it hoists eight per-row-block registers out of the loop and adds the slot offset to each: two VALU
   // instructions per read, each of which takes the matrix pipe's issue port)
-  typedef const s8v __attribute__((address_space(3))) lds_s8v;
   unsigned laneA = 0, laneB = 0, pa0 = 0, pa1 = 0, pb0 = 0, pb1 = 0;
   (void)pa1;
-#define RF_LANE_BASES()                                                                                          \
-  {                                                                                                              \
-    if (!A_KS) {                                                                                                 \
-      const int row = wm * 128 + (lane_m & 15);                                                                  \
-      laneA = lds0 + row * 128 + ((((lane_m >> 4)) ^ kc_swz(row)) << 4);                                         \
-    } else { /* k-strided image: k row r, 32-byte block (row block ^ swizzle): the row block mi enters by XOR, see fa_ */ \
-      const int p = lane_m & 15;                                                                                 \
-      const int r = (lane_m >> 4) * 8 + (p >> 2);                                                                \
-      laneA = lds0 + r * 512 + ((p & 3) << 3) + wm * 256 + (ks_swz(r) << 5);                                     \
-    }                                                                                                            \
-    if (!B_KS) {                                                                                                 \
-      const int j = lane_m & 15;                                                                                 \
-      const int row = wn * 64 + (j >> 2) * 8 + (j & 3);                                                          \
-      laneB = lds0 + row * 128 + ((((lane_m >> 4)) ^ kcb_swz(row)) << 4);                                        \
-    } else {                                                                                                     \
-      const int p = lane_m & 15;                                                                                 \
-      const int r = (lane_m >> 4) * 8 + (p >> 2);                                                                \
-      laneB = lds0 + r * 512 + (((wn * 4 + ((p & 3) >> 1)) ^ ks_swz(r)) << 5) + (((p & 3) & 1) << 4);            \
-    }                                                                                                            \
-  }
-#define RF_STEP_BASES()                                          \
-  {                                                              \
-    pa0 = laneA + sa_off;                                        \
-    asm volatile("" : "+v"(pa0));                                \
-    if (!A_KS) {                                                 \
-      pa1 = pa0 ^ 64u;                                           \
-      asm volatile("" : "+v"(pa1));                              \
-    }                                                            \
-    pb0 = laneB + sb_off;                                        \
-    asm volatile("" : "+v"(pb0));                                \
-    pb1 = pb0 ^ 64u;                                             \
-    asm volatile("" : "+v"(pb1));                                \
-  }
-  typedef s4v __attribute__((address_space(3))) lds_s4v;
-  auto tr2_ = [&](unsigned addr) -> bf16x8 {   // the two transposed 8-byte reads of a k-strided fragment (k rows r and r + 4)
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(size_t)addr);
-#if defined(RF_EXP_HALFTR)     /* timing only (wrong operands): one transposed read per fragment instead of two */
-    const s4v hi = lo;
-#else
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(size_t)(addr + 4u * 512u));
-#endif
-    s8v v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
-  auto fa_ = [&](int ks, int mi) -> bf16x8 {
-    if constexpr (!A_KS) {
-      const s8v v = *reinterpret_cast<lds_s8v*>((size_t)((ks ? pa1 : pa0) + (unsigned)mi * 2048u));
-      return __builtin_bit_cast(bf16x8, v);
-    } else {
-      // (block ^ swizzle) << 5 with block = 8 wm + mi: the low three bits of the block are mi, so the row block is an XOR on
-      // address bits 5-7 (one VALU instruction per fragment; the k half is an immediate: 32 k rows x 512 B)
-#if defined(RF_EXP_NOXOR)      /* timing only (wrong operands): what do the 16 address XORs of a TN K step cost? */
-      return tr2_(pa0 + (unsigned)mi * 32u + (unsigned)ks * 16384u);
-#else
-      return tr2_((pa0 ^ ((unsigned)mi << 5)) + (unsigned)ks * 16384u);
-#endif
-    }
-  };
-  auto fb_ = [&](int ks, int ni) -> bf16x8 {
-    if constexpr (!B_KS) {
-      const s8v v = *reinterpret_cast<lds_s8v*>((size_t)((ks ? pb1 : pb0) + (unsigned)((ni >> 1) * 4096 + (ni & 1) * 512)));
-      return __builtin_bit_cast(bf16x8, v);
-    } else {
-      // column block (4 wn + 2 (ni >> 1) + ...) ^ swizzle: ni >> 1 flips address bit 6 (pb1), ni & 1 adds 8 bytes
-      return tr2_(((ni >> 1) ? pb1 : pb0) + (unsigned)ks * 16384u + (unsigned)(ni & 1) * 8u);
-    }
-  };
-#define RF_FA(ks, mi) fa_(ks, mi)
-#define RF_FB(ks, ni) fb_(ks, ni)
+#define RF_LANE_BASES() RING_LANE_BASES(A_KS, B_KS, 128, lds0, lane_m)
+#define RF_STEP_BASES() RING_STEP_BASES(A_KS)
+#define RF_FA(ks, mi) ring_frag_a<A_KS>(pa0, pa1, ks, mi)
+#define RF_FB(ks, ni) ring_frag_b<B_KS>(pb0, pb1, ks, ni)
   // (Z: the MFMA starts its accumulator -- the k half 0 groups of a tile's first step; saves zeroing 128 registers per tile)
-#define RF_M(a, b, pr, j, ni, Z)                                                                                        \
-  if (!(ABL & 4)) acc[2 * (pr) + (j)][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                                    \
-      b[ni], a[j], (Z) ? (f4v){0.0f, 0.0f, 0.0f, 0.0f} : acc[2 * (pr) + (j)][ni], 0, 0, 0)
-  // one 8-MFMA group (A fragments a[0..1] x B fragments b[0..3] -> accumulator rows 2 pr, 2 pr + 1), one filler statement per MFMA
-#define RF_GROUPZ(Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7)             \
-  RF_M(a, b, pr, 0, 0, Z); RF_SB(); f0; RF_SB();                              \
-  RF_M(a, b, pr, 0, 1, Z); RF_SB(); f1; RF_SB();                              \
-  RF_M(a, b, pr, 0, 2, Z); RF_SB(); f2; RF_SB();                              \
-  RF_M(a, b, pr, 0, 3, Z); RF_SB(); f3; RF_SB();                              \
-  RF_M(a, b, pr, 1, 0, Z); RF_SB(); f4; RF_SB();                              \
-  RF_M(a, b, pr, 1, 1, Z); RF_SB(); f5; RF_SB();                              \
-  RF_M(a, b, pr, 1, 2, Z); RF_SB(); f6; RF_SB();                              \
-  RF_M(a, b, pr, 1, 3, Z); RF_SB(); f7; RF_SB();
-#define RF_GROUP(a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) RF_GROUPZ(false, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7)
+#define RF_M(a, b, mi, ni, Z)                                             \
+  if (!(ABL & 4)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(   \
+      b[ni], a[(mi) & 1], (Z) ? (f4v){0.0f, 0.0f, 0.0f, 0.0f} : acc[mi][ni], 0, 0, 0)
+  // (one filler statement per MFMA)
+#define RF_GROUPZ(Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) G8_GROUP(RF_M, Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7)
+#define RF_GROUP(a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) G8_GROUP(RF_M, false, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7)
 #define RF_PB(J) if (!(ABL & (8 | 16))) glds16_piece<J>(b_ptr, vb[J], b_dst)
 // RF_PBF: B(t+1)'s pieces in a tile's FIRST step (no held group in front of it); in the other steps they ride on the held group
 #define RF_PBF(FIRST, J) if (FIRST) RF_PB(J)
@@ -848,32 +802,11 @@ __global__ __launch_bounds__(512, 2) void gemm256f_kernel(const GroupArgs ga) {
     // ... and the B slot consumed last (free until this wave's own pieces of the next tile's B(1) go there, in its first step):
     // a second 4 KiB per wave, for the epilogue's operand tile (epilogue256, IN_DMA)
     unsigned char* scr2 = smem + ((2 * PP_B_BASE + TILE2_BYTES) - sb_off) + wid * 4096;
-    if (!B_KS) {
-      switch (epi) {
-        case 0: epilogue256<(0), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        case EPI_BIAS: epilogue256<(EPI_BIAS), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        case EPI_BIAS | EPI_GELU: epilogue256<(EPI_BIAS | EPI_GELU), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        case EPI_BIAS | EPI_GELU_FWD: epilogue256<(EPI_BIAS | EPI_GELU_FWD), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        case EPI_BIAS | EPI_ADD: epilogue256<(EPI_BIAS | EPI_ADD), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        case EPI_BIAS | EPI_ADD | EPI_DROP: epilogue256<(EPI_BIAS | EPI_ADD | EPI_DROP), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-        default: epilogue256<-1, 8, true, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2); break;
-      }
-    } else if (A_KS && epi == EPI_RMW32) {
-      epilogue256<(EPI_RMW32), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else if (A_KS && epi == EPI_STORE32) {   // weight gradients of the first backward pass after an optimizer step: overwrite
-      epilogue256<(EPI_STORE32), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else if (!A_KS && epi == EPI_ADD) {
-      epilogue256<(EPI_ADD), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else if (!A_KS && epi == 0) {
-      epilogue256<(0), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else if (!A_KS && epi == (EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS)) {
-      // FFN-down dgrad: x GELU' + column sums (the two-stage kernel keeps this one generic: specialised there it spilled)
-      epilogue256<(EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else if (!A_KS && epi == EPI_DGELU) {
-      epilogue256<(EPI_DGELU), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    } else {
-      epilogue256<-1, 8, true, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2);
-    }
+#define EPI_RUN(E) epilogue256<(E), 8, false, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2)
+#define EPI_RUN_GENERIC() epilogue256<-1, 8, true, true>(g, acc, m0, n0, wm, wn, lane_e, scr, scr2)
+    DISPATCH_EPILOGUE(A_KS, B_KS, true)
+#undef EPI_RUN
+#undef EPI_RUN_GENERIC
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // scratch reads done before this wave's next DMA lands there
     G2_T(2)
     ++tile_no;
@@ -940,59 +873,26 @@ __global__ __launch_bounds__(512, 2) void gemm128i_kernel(const GroupArgs ga) {
   const int nt = g.K / BK2;
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void*)smem);
   unsigned va[2], vb[4];
+  // (A's two offsets piece by piece: through stage_voff<false, false> the same instructions come out in another order)
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int row = (wid * 2 + j) * 8 + (lane >> 3);
-    va[j] = (unsigned)(row * g.lda + (((lane & 7) ^ kc_swz(row)) << 3)) * 2u - (unsigned)j * 1024u;
-  }
+  for (int j = 0; j < 2; ++j) va[j] = piece_voff<false, false>(wid * 2 + j, g.lda, lane) - (unsigned)j * 1024u;
   stage_voff<B_KS, true>(g.ldb, wid, lane, vb);
   const bf16_t* a_base = uniform_ptr(g.A + (size_t)m0 * g.lda);
   const bf16_t* b_base = uniform_ptr(B_KS ? g.B + n0 : g.B + (size_t)n0 * g.ldb);
   const size_t b_kstep = B_KS ? (size_t)BK2 * g.ldb : (size_t)BK2;
   const unsigned a_dst0 = lds0 + wid * 2048, b_dst0 = lds0 + R2_B_BASE + wid * 4096;
   unsigned laneA, laneB;
-  {
-    const int row = wm * 64 + (lane & 15);
-    laneA = lds0 + row * 128 + ((((lane >> 4)) ^ kc_swz(row)) << 4);
-    if (!B_KS) {
-      const int j = lane & 15;
-      const int brow = wn * 64 + (j >> 2) * 8 + (j & 3);
-      laneB = lds0 + R2_B_BASE + brow * 128 + ((((lane >> 4)) ^ kcb_swz(brow)) << 4);
-    } else {
-      const int p = lane & 15;
-      const int r = (lane >> 4) * 8 + (p >> 2);
-      laneB = lds0 + R2_B_BASE + r * 512 + (((wn * 4 + ((p & 3) >> 1)) ^ ks_swz(r)) << 5) + (((p & 3) & 1) << 4);
-    }
-  }
-  typedef const s8v __attribute__((address_space(3))) lds_s8v;
-  typedef s4v __attribute__((address_space(3))) lds_s4v;
-  auto tr2_ = [&](unsigned addr) -> bf16x8 {
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(size_t)addr);
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(size_t)(addr + 4u * 512u));
-    s8v v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  RING_LANE_BASES(false, B_KS, 64, lds0 + R2_B_BASE, lane)
   unsigned pa0 = laneA, pa1 = laneA ^ 64u, pb0 = laneB, pb1 = laneB ^ 64u;
-  auto fa_ = [&](int ks, int mi) -> bf16x8 {
-    const s8v v = *reinterpret_cast<lds_s8v*>((size_t)((ks ? pa1 : pa0) + (unsigned)mi * 2048u));
-    return __builtin_bit_cast(bf16x8, v);
-  };
-  auto fb_ = [&](int ks, int ni) -> bf16x8 {
-    if constexpr (!B_KS) {
-      const s8v v = *reinterpret_cast<lds_s8v*>((size_t)((ks ? pb1 : pb0) + (unsigned)((ni >> 1) * 4096 + (ni & 1) * 512)));
-      return __builtin_bit_cast(bf16x8, v);
-    } else {
-      return tr2_(((ni >> 1) ? pb1 : pb0) + (unsigned)ks * 16384u + (unsigned)(ni & 1) * 8u);
-    }
-  };
+  // (lambdas where gemm256f_kernel has macros: with macros this kernel's instructions come out in another order)
+  auto fa_ = [&](int ks, int mi) -> bf16x8 { return ring_frag_a<false>(pa0, pa1, ks, mi); };
+  auto fb_ = [&](int ks, int ni) -> bf16x8 { return ring_frag_b<B_KS>(pb0, pb1, ks, ni); };
   // prologue: stages 0 and 1 (a one-step tile re-reads stage 0 into slot 1: nobody reads it)
   {
     const int t1 = nt > 1 ? 1 : 0;
-    glds16_pair<0>(a_base, va[0], va[1], a_dst0);
+    glds16_pair(a_base, va[0], va[1], a_dst0);
     glds16_quad(b_base, vb[0], vb[1], vb[2], vb[3], b_dst0);
-    glds16_pair<0>(a_base + (size_t)t1 * BK2, va[0], va[1], a_dst0 + R2_A_BYTES);
+    glds16_pair(a_base + (size_t)t1 * BK2, va[0], va[1], a_dst0 + R2_A_BYTES);
     glds16_quad(b_base + (size_t)t1 * b_kstep, vb[0], vb[1], vb[2], vb[3], b_dst0 + TILE2_BYTES);
   }
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -1002,19 +902,11 @@ __global__ __launch_bounds__(512, 2) void gemm128i_kernel(const GroupArgs ga) {
   f4v acc[4][4];
   const f4v zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
   bf16x8 b0[4], b1[4], a0[2], a1[2];
-#define ISB() __builtin_amdgcn_sched_barrier(0)
+#define ISB() G8_SB()
 #define INOP (void)0
 #define IMF(a, b, mi, ni, Z) \
   acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ni], a[(mi) & 1], (Z) ? zero4 : acc[mi][ni], 0, 0, 0)
-#define IGROUP(Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) \
-  IMF(a, b, 2 * (pr), 0, Z); ISB(); f0; ISB();               \
-  IMF(a, b, 2 * (pr), 1, Z); ISB(); f1; ISB();               \
-  IMF(a, b, 2 * (pr), 2, Z); ISB(); f2; ISB();               \
-  IMF(a, b, 2 * (pr), 3, Z); ISB(); f3; ISB();               \
-  IMF(a, b, 2 * (pr) + 1, 0, Z); ISB(); f4; ISB();           \
-  IMF(a, b, 2 * (pr) + 1, 1, Z); ISB(); f5; ISB();           \
-  IMF(a, b, 2 * (pr) + 1, 2, Z); ISB(); f6; ISB();           \
-  IMF(a, b, 2 * (pr) + 1, 3, Z); ISB(); f7; ISB();
+#define IGROUP(Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7) G8_GROUP(IMF, Z, a, b, pr, f0, f1, f2, f3, f4, f5, f6, f7)
 #define IPB(J) glds16_piece<J>(pb_src, vb[J], b_dst)
 #define IPA(J) glds16_piece<J>(pa_src, va[J], a_dst)
   // groups 0-2 of a step (group 3 is held across the barrier), the wait, the barrier, the slot rotation
@@ -1031,14 +923,7 @@ __global__ __launch_bounds__(512, 2) void gemm128i_kernel(const GroupArgs ga) {
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                                                \
     __builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
     pp_barrier();                                                                                                   \
-    pa0 = laneA + sa_off;                                                                                           \
-    asm volatile("" : "+v"(pa0));                                                                                   \
-    pa1 = pa0 ^ 64u;                                                                                                \
-    asm volatile("" : "+v"(pa1));                                                                                   \
-    pb0 = laneB + sb_off;                                                                                           \
-    asm volatile("" : "+v"(pb0));                                                                                   \
-    pb1 = pb0 ^ 64u;                                                                                                \
-    asm volatile("" : "+v"(pb1));                                                                                   \
+    RING_STEP_BASES(false)                                                                                          \
   }
   // step 0: first fragments, the B pieces of stage 2 in a block, groups 0-2
   {
@@ -1080,85 +965,39 @@ __global__ __launch_bounds__(512, 2) void gemm128i_kernel(const GroupArgs ga) {
   int lane_e = lane;
   asm volatile("" : "+v"(lane_e));
   unsigned char* scr = smem + wid * 4096;
-  if (!B_KS) {
-    switch (epi) {
-      case 0: epilogue256<0, 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      case EPI_BIAS: epilogue256<EPI_BIAS, 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      case EPI_BIAS | EPI_GELU: epilogue256<(EPI_BIAS | EPI_GELU), 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      case EPI_BIAS | EPI_GELU_FWD: epilogue256<(EPI_BIAS | EPI_GELU_FWD), 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      case EPI_BIAS | EPI_ADD: epilogue256<(EPI_BIAS | EPI_ADD), 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      case EPI_BIAS | EPI_ADD | EPI_DROP: epilogue256<(EPI_BIAS | EPI_ADD | EPI_DROP), 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-      default: epilogue256<-1, 4>(g, acc, m0, n0, wm, wn, lane_e, scr); break;
-    }
-  } else if (epi == EPI_ADD) {
-    epilogue256<EPI_ADD, 4>(g, acc, m0, n0, wm, wn, lane_e, scr);
-  } else if (epi == 0) {
-    epilogue256<0, 4>(g, acc, m0, n0, wm, wn, lane_e, scr);
-  } else {
-    epilogue256<-1, 4>(g, acc, m0, n0, wm, wn, lane_e, scr);
-  }
+#define EPI_RUN(E) epilogue256<(E), 4>(g, acc, m0, n0, wm, wn, lane_e, scr)
+#define EPI_RUN_GENERIC() epilogue256<-1, 4>(g, acc, m0, n0, wm, wn, lane_e, scr)
+  DISPATCH_EPILOGUE(false, B_KS, false)
+#undef EPI_RUN
+#undef EPI_RUN_GENERIC
 }
 
-template <bool B_KS>
-static int launch128i(const GroupArgs& ga, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_done{0};
-  const int r = kbner_set_max_lds_once(attr_done, reinterpret_cast<const void*>(gemm128i_kernel<B_KS>), R2_LDS_BYTES);
-  if (r) return r;
-  hipLaunchKernelGGL((gemm128i_kernel<B_KS>), dim3(ga.total_tiles), dim3(512), R2_LDS_BYTES, stream, ga);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
-// one_tile_each: grid = number of tiles, every workgroup computes exactly ONE (its cursors find no next tile): the hardware
-// dispatcher then hands tiles to CUs as they become free -- the dynamic schedule of the long-K launches at N > 1 (see
-// gemm_grouped_impl), at the price of a cold prologue and an exposed epilogue per tile, which a K >= 3072 tile does not notice.
-template <bool A_KS, bool B_KS, int ABL = 0, bool MIDSYNC = false>
-static int launch256f(const GroupArgs& ga, hipStream_t stream, bool one_tile_each = false) {
-  static std::atomic<unsigned long long> attr_done{0};
-  const int r = kbner_set_max_lds_once(attr_done, reinterpret_cast<const void*>(gemm256f_kernel<A_KS, B_KS, ABL, MIDSYNC>), PP_LDS_BYTES);
-  if (r) return r;
-  const int grid = (one_tile_each || ga.total_tiles < ga.ncu) ? ga.total_tiles : ga.ncu;
-  hipLaunchKernelGGL((gemm256f_kernel<A_KS, B_KS, ABL, MIDSYNC>), dim3(grid), dim3(512), PP_LDS_BYTES, stream, ga);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-
-// which main loop the 256-row static launches use: 1 = the interleaved ring loop (gemm256f_kernel, default), 0 = the two-stage loop
-// of rounds 1-3 (gemm256_kernel; also what the 128-row and the dynamic-tile launches run).  Process-wide, atomic; set through
-// kbner_gemm_set_variant (include/kbner.h).  Trace builds (-DG2_TRACE) read compile-time ablations of the ring loop from bits 12-15.
+// Which main loop the 256-row static launches use: bit 0 = the ring kernels (gemm256f_kernel; gemm128i_kernel for 128-row tiles),
+// clear = the two-stage loop of rounds 1-3 (gemm256_kernel, also what the tile-drawing dynamic launches run); bits 1 and 2 = the
+// ring kernel's XCD meetings (gemm_grouped_impl).  Process-wide, atomic; set through kbner_gemm_set_variant (include/kbner.h).
 static std::atomic<int> g_gemm_variant{KBNER_GEMM_VARIANT_DEFAULT};
 
-template <bool A_KS, bool B_KS, bool DYN, int TM = 256>
-static int launch256(const GroupArgs& ga, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_done{0};   // per template instantiation, one bit per device
-  const int r = kbner_set_max_lds_once(attr_done, reinterpret_cast<const void*>(gemm256_kernel<A_KS, B_KS, DYN, TM>), G2_LDS_BYTES);
+// The one launcher: raise the kernel's dynamic-LDS limit once per device, launch `grid` workgroups of 8 waves, map the error.
+// grid = one workgroup per CU walking the tiles (persistent), or the number of tiles: every workgroup then computes exactly ONE
+// (a ring kernel's cursors find no next tile) and the hardware dispatcher hands tiles to CUs as they become free -- the dynamic
+// schedule of the long-K launches (see gemm_grouped_impl), at the price of a cold prologue and an exposed epilogue per tile, which
+// a K >= 1024 tile does not notice; gemm128i_kernel is always launched that way.
+template <void (*KERNEL)(const GroupArgs), int LDS_BYTES>
+static int launch_gemm(const GroupArgs& ga, int grid, hipStream_t stream) {
+  static std::atomic<unsigned long long> attr_done{0};   // per kernel, one bit per device
+  const int r = kbner_set_max_lds_once(attr_done, reinterpret_cast<const void*>(KERNEL), LDS_BYTES);
   if (r) return r;
-  const int grid = ga.total_tiles < ga.ncu ? ga.total_tiles : ga.ncu;
-  hipLaunchKernelGGL((gemm256_kernel<A_KS, B_KS, DYN, TM>), dim3(grid), dim3(512), G2_LDS_BYTES, stream, ga);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(512), LDS_BYTES, stream, ga);
+  KBNER_LAUNCH_RET();
 }
-
-static int device_cu_count() { return kbner_cu_count(); }
-
-// public mirror of GemmProblem (include/kbner.h: kbner_gemm_problem)
-struct kbner_gemm_problem {
-  const bf16_t* A;
-  const bf16_t* B;
-  bf16_t* C;
-  float* C32;
-  const float* bias;
-  const bf16_t* addend;
-  const bf16_t* aux;
-  bf16_t* out2;
-  float* colsum;
-  int M, N, K;
-  int lda, ldb, ldc, ldc32, ldadd, ldaux, ldout2;
-  int epi;
-  float alpha;
-  uint32_t drop_seed;
-  uint32_t drop_thresh;
-};
+template <bool A_KS, bool B_KS, bool DYN, int TM = 256>
+static int launch256(const GroupArgs& ga, int grid, hipStream_t stream) {
+  return launch_gemm<gemm256_kernel<A_KS, B_KS, DYN, TM>, G2_LDS_BYTES>(ga, grid, stream);
+}
+template <bool A_KS, bool B_KS, int ABL = 0, bool MIDSYNC = false>
+static int launch256f(const GroupArgs& ga, int grid, hipStream_t stream) {
+  return launch_gemm<gemm256f_kernel<A_KS, B_KS, ABL, MIDSYNC>, PP_LDS_BYTES>(ga, grid, stream);
+}
 
 #ifdef G2_TRACE
 extern "C" int kbner_debug_read_trace(unsigned long long* out) {
@@ -1193,7 +1032,7 @@ static constexpr int kVariantBits = 7 | 16 | 32 | G2_TRACE_VARIANT_BITS;
 static bool wants_128x(int layout, int nprob, const kbner_gemm_problem* probs, bool dyn, int variant) {
   if (dyn || nprob != 1 || !(variant & (16 | 32))) return false;
   const kbner_gemm_problem& s = probs[0];
-  return kbner_can128x(layout, s.M, s.N, s.K, s.epi) && (long)(s.M / 128) * (s.N / T2) >= 2L * device_cu_count();
+  return kbner_can128x(layout, s.M, s.N, s.K, s.epi) && (long)(s.M / 128) * (s.N / T2) >= 2L * kbner_cu_count();
 }
 static int launch_128x(int variant, int layout, const GroupArgs& ga, hipStream_t st) {
   return (variant & 32) ? kbner_launch128s(layout, ga, st) : kbner_launch128x(layout, ga, st);
@@ -1205,6 +1044,7 @@ static int launch_128x(int, int, const GroupArgs&, hipStream_t) { return KBNER_E
 #endif
 
 static int pick_tile_rows(int layout, int nprob, const kbner_gemm_problem* probs, bool dyn, int variant);
+static int gemm_grouped_impl(int layout, int nprob, const kbner_gemm_problem* probs, int* sched, void* stream);
 
 extern "C" {
 
@@ -1216,11 +1056,6 @@ int kbner_gemm_tile_rows(int layout, int M, int N) {
   p.N = N;
   return pick_tile_rows(layout, 1, &p, false, g_gemm_variant.load(std::memory_order_relaxed));
 }
-
-// Grouped GEMM: nprob (1..16) problems of the SAME layout in one launch.
-// Constraints per problem: M % 256 == 0, N % 256 == 0, K % 64 == 0, lda/ldb % 8 == 0.
-static int gemm_grouped_impl(int layout, int nprob, const kbner_gemm_problem* probs, int* sched, void* stream);
-static int pick_tile_rows(int layout, int nprob, const kbner_gemm_problem* probs, bool dyn, int variant);
 
 int kbner_gemm_set_variant(int variant) {
   KBNER_CHECK_ARG(variant >= 0 && !(variant & ~kVariantBits));   // only the bits that mean something in THIS build
@@ -1260,41 +1095,57 @@ static int pick_tile_rows(int layout, int nprob, const kbner_gemm_problem* probs
     if (s.M % T2 != 0 || s.N % T2 != 0) return T2;
     tiles += (long)(s.M / T2) * (s.N / T2);
   }
-  return 2 * tiles <= device_cu_count() ? 128 : T2;
+  return 2 * tiles <= kbner_cu_count() ? 128 : T2;
 }
 
+// The one place a public problem record becomes a kernel descriptor: checks it, copies it (kbner_bf16 and bf16_t are both uint16_t).
+static int to_gemm_problem(const kbner_gemm_problem& s, int tile_begin, GemmProblem& d) {
+  static_assert(std::is_same<kbner_bf16, bf16_t>::value, "the ABI's and the kernels' bf16 storage type");
+  KBNER_CHECK_ARG(s.M > 0 && s.N > 0 && s.K > 0 && s.M % T2 == 0 && s.N % T2 == 0 && s.K % BK2 == 0);
+  KBNER_CHECK_ARG(s.A != nullptr && s.B != nullptr && s.lda % 8 == 0 && s.ldb % 8 == 0);
+  if (s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32)) {
+    KBNER_CHECK_ARG(s.C32 != nullptr && s.ldc32 >= s.N && s.ldc32 % 4 == 0);
+  } else {
+    KBNER_CHECK_ARG(s.C != nullptr && s.ldc >= s.N && s.ldc % 8 == 0);
+  }
+  if (s.epi & EPI_BIAS) KBNER_CHECK_ARG(s.bias != nullptr);
+  if (s.epi & EPI_ADD) KBNER_CHECK_ARG(s.addend != nullptr && s.ldadd % 8 == 0);
+  if (s.epi & EPI_DGELU) KBNER_CHECK_ARG(s.aux != nullptr && s.ldaux % 8 == 0);
+  if (s.epi & EPI_GELU) KBNER_CHECK_ARG(s.out2 != nullptr && s.ldout2 % 8 == 0);
+  if (s.epi & EPI_COLSUM) KBNER_CHECK_ARG(s.colsum != nullptr && !(s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32)));
+  if (s.epi & EPI_COLSUM_WS) KBNER_CHECK_ARG((s.epi & EPI_COLSUM) != 0 && s.N % 4 == 0);
+  if (s.epi & EPI_STORE32) KBNER_CHECK_ARG(s.epi == EPI_STORE32);
+  if (s.epi & EPI_DROP) KBNER_CHECK_ARG(!(s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_COLSUM | EPI_GELU | EPI_DGELU | EPI_GELU_FWD)));
+  if (s.epi & EPI_GELU_FWD) KBNER_CHECK_ARG(!(s.epi & (EPI_GELU | EPI_DGELU | EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32 | EPI_COLSUM)));
+  d.A = s.A; d.B = s.B; d.C = s.C; d.C32 = s.C32;
+  d.bias = s.bias; d.addend = s.addend; d.aux = s.aux; d.out2 = s.out2; d.colsum = s.colsum;
+  d.M = s.M; d.N = s.N; d.K = s.K;
+  d.lda = s.lda; d.ldb = s.ldb; d.ldc = s.ldc; d.ldc32 = s.ldc32; d.ldadd = s.ldadd; d.ldaux = s.ldaux; d.ldout2 = s.ldout2;
+  d.epi = s.epi;
+  d.alpha = s.alpha;
+  d.tile_begin = tile_begin;
+  d.drop_seed = s.drop_seed;
+  d.drop_thresh = (s.epi & EPI_DROP) ? s.drop_thresh : 0u;
+  d.pad_ = 0;
+  return 0;
+}
+
+// Grouped GEMM: nprob (1..16) problems of the SAME layout in one launch.
+// Constraints per problem: M % 256 == 0, N % 256 == 0, K % 64 == 0, lda/ldb % 8 == 0.
 static int gemm_grouped_impl(int layout, int nprob, const kbner_gemm_problem* probs, int* sched, void* stream) {
   KBNER_CHECK_ARG(layout >= 0 && layout <= 2 && nprob >= 1 && nprob <= G2_MAXP && probs != nullptr);
   GroupArgs ga;
   ga.nprob = nprob;
   const int variant = g_gemm_variant.load(std::memory_order_relaxed);   // the ONE read of the switch for this launch
   const int TM = pick_tile_rows(layout, nprob, probs, sched != nullptr, variant);
-  int tiles = 0;
+  int tiles = 0, min_k = 0x7fffffff, max_k = 0;
   for (int i = 0; i < nprob; ++i) {
-    const kbner_gemm_problem& s = probs[i];
-    KBNER_CHECK_ARG(s.M > 0 && s.N > 0 && s.K > 0 && s.M % T2 == 0 && s.N % T2 == 0 && s.K % BK2 == 0);
-    KBNER_CHECK_ARG(s.A != nullptr && s.B != nullptr && s.lda % 8 == 0 && s.ldb % 8 == 0);
-    if (s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32)) {
-      KBNER_CHECK_ARG(s.C32 != nullptr && s.ldc32 >= s.N && s.ldc32 % 4 == 0);
-    } else {
-      KBNER_CHECK_ARG(s.C != nullptr && s.ldc >= s.N && s.ldc % 8 == 0);
-    }
-    if (s.epi & EPI_BIAS) KBNER_CHECK_ARG(s.bias != nullptr);
-    if (s.epi & EPI_ADD) KBNER_CHECK_ARG(s.addend != nullptr && s.ldadd % 8 == 0);
-    if (s.epi & EPI_DGELU) KBNER_CHECK_ARG(s.aux != nullptr && s.ldaux % 8 == 0);
-    if (s.epi & EPI_GELU) KBNER_CHECK_ARG(s.out2 != nullptr && s.ldout2 % 8 == 0);
-    if (s.epi & EPI_COLSUM) KBNER_CHECK_ARG(s.colsum != nullptr && !(s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32)));
-    if (s.epi & EPI_COLSUM_WS) KBNER_CHECK_ARG((s.epi & EPI_COLSUM) != 0 && s.N % 4 == 0);
-    if (s.epi & EPI_STORE32) KBNER_CHECK_ARG(s.epi == EPI_STORE32);
-    if (s.epi & EPI_DROP) KBNER_CHECK_ARG(!(s.epi & (EPI_ATOMIC32 | EPI_RMW32 | EPI_COLSUM | EPI_GELU | EPI_DGELU | EPI_GELU_FWD)));
-    if (s.epi & EPI_GELU_FWD) KBNER_CHECK_ARG(!(s.epi & (EPI_GELU | EPI_DGELU | EPI_ATOMIC32 | EPI_RMW32 | EPI_STORE32 | EPI_COLSUM)));
-    GemmProblem& d = ga.p[i];
-    d.A = s.A; d.B = s.B; d.C = s.C; d.C32 = s.C32; d.bias = s.bias; d.addend = s.addend; d.aux = s.aux; d.out2 = s.out2; d.colsum = s.colsum;
-    d.M = s.M; d.N = s.N; d.K = s.K; d.lda = s.lda; d.ldb = s.ldb; d.ldc = s.ldc; d.ldc32 = s.ldc32; d.ldadd = s.ldadd;
-    d.ldaux = s.ldaux; d.ldout2 = s.ldout2; d.epi = s.epi; d.alpha = s.alpha; d.tile_begin = tiles; d.pad_ = 0;
-    d.drop_seed = s.drop_seed; d.drop_thresh = (s.epi & EPI_DROP) ? s.drop_thresh : 0u;
+    const int r = to_gemm_problem(probs[i], tiles, ga.p[i]);
+    if (r) return r;
     ga.tile_begin[i] = tiles;
-    tiles += (s.M / TM) * (s.N / T2);
+    tiles += (probs[i].M / TM) * (probs[i].N / T2);
+    min_k = probs[i].K < min_k ? probs[i].K : min_k;
+    max_k = probs[i].K > max_k ? probs[i].K : max_k;
   }
   for (int i = nprob; i < G2_MAXP; ++i) {
     ga.p[i] = ga.p[0];
@@ -1302,18 +1153,14 @@ static int gemm_grouped_impl(int layout, int nprob, const kbner_gemm_problem* pr
     ga.tile_begin[i] = 0x7fffffff;
   }
   ga.total_tiles = tiles;
-  ga.ncu = device_cu_count();
+  ga.ncu = kbner_cu_count();
   // tile-boundary sync of the ring kernel (variant bit 1): every problem's K loop is long enough for the drift to matter
-  int min_k = 0x7fffffff;
-  for (int i = 0; i < nprob; ++i) min_k = probs[i].K < min_k ? probs[i].K : min_k;
-  int max_k = 0;
-  for (int i = 0; i < nprob; ++i) max_k = probs[i].K > max_k ? probs[i].K : max_k;
-  const int gv = variant;
-  ga.pad_ = ((gv & 2) && min_k >= 256 * BK2 && tiles >= 2 * ga.ncu) ? 1 : 0;
-  if (ga.pad_ && (gv & 4) && layout == 2 && min_k == max_k && min_k >= 512 * BK2) ga.pad_ |= 256 << 8;   // + every 256 K steps inside a tile
+  ga.pad_ = ((variant & 2) && min_k >= 256 * BK2 && tiles >= 2 * ga.ncu) ? 1 : 0;
+  if (ga.pad_ && (variant & 4) && layout == 2 && min_k == max_k && min_k >= 512 * BK2) ga.pad_ |= 256 << 8;   // + every 256 K steps inside a tile
   ga.sched = sched;
   hipStream_t st = (hipStream_t)stream;
-  if (sched != nullptr && (gv & 1) && min_k >= 1024) {
+  const int walk = tiles < ga.ncu ? tiles : ga.ncu;   // grid of a persistent launch (launch_gemm)
+  if (sched != nullptr && (variant & 1) && min_k >= 1024) {
     // Dynamic scheduling (round 5): the ring kernel, ONE workgroup per tile.  No draw, no counters: the dispatcher places the
     // 768 (weight gradients) ... 4096 workgroups on whatever CUs are free, which is exactly what a step that shares the GPU with a
     // collective needs (tools/contention_lab.py: 8 CUs held -> static walk +45 %, this +13 %, the tile draw on the two-stage loop
@@ -1322,52 +1169,57 @@ static int gemm_grouped_impl(int layout, int nprob, const kbner_gemm_problem* pr
     // shorter than 16 steps (none in the encoder) keep the draw below.  `sched` is left untouched.
     ga.pad_ = 0;
     switch (layout) {
-      case 0: return launch256f<false, false>(ga, st, true);
-      case 1: return launch256f<false, true>(ga, st, true);
-      default: return launch256f<true, true>(ga, st, true);
+      case 0: return launch256f<false, false>(ga, tiles, st);
+      case 1: return launch256f<false, true>(ga, tiles, st);
+      default: return launch256f<true, true>(ga, tiles, st);
     }
   }
   if (sched != nullptr) {
     switch (layout) {
-      case 0: return launch256<false, false, true>(ga, st);
-      case 1: return launch256<false, true, true>(ga, st);
-      default: return launch256<true, true, true>(ga, st);
+      case 0: return launch256<false, false, true>(ga, walk, st);
+      case 1: return launch256<false, true, true>(ga, walk, st);
+      default: return launch256<true, true, true>(ga, walk, st);
     }
   }
   if (TM == 128 && wants_128x(layout, nprob, probs, sched != nullptr, variant)) return launch_128x(variant, layout, ga, st);
   if (TM == 128) {
     // the interleaved ring, or (bit 0 clear) the two-stage loop's 128-row tiles: the bit-identity reference
-    if (variant & 1) return layout == 0 ? launch128i<false>(ga, st) : launch128i<true>(ga, st);
-    return layout == 0 ? launch256<false, false, false, 128>(ga, st) : launch256<false, true, false, 128>(ga, st);
+    if (variant & 1)
+      return layout == 0 ? launch_gemm<gemm128i_kernel<false>, R2_LDS_BYTES>(ga, tiles, st)
+                         : launch_gemm<gemm128i_kernel<true>, R2_LDS_BYTES>(ga, tiles, st);
+    return layout == 0 ? launch256<false, false, false, 128>(ga, walk, st) : launch256<false, true, false, 128>(ga, walk, st);
   }
 #ifdef G2_TRACE
   if ((variant & 1) && layout == 2 && (variant & 0xF000)) {   // cycle-accounting ablations, TN: no DMA wait / no DMA
     switch ((variant >> 12) & 15) {
-      case 4: return launch256f<true, true, 64>(ga, st);
-      default: return launch256f<true, true, 8>(ga, st);
+      case 4: return launch256f<true, true, 64>(ga, walk, st);
+      default: return launch256f<true, true, 8>(ga, walk, st);
     }
   }
   if ((variant & 1) && layout == 0 && (variant & 0xF000)) {   // cycle-accounting ablations, NT
     switch ((variant >> 12) & 15) {
-      case 1: return launch256f<false, false, 1>(ga, st);
-      case 2: return launch256f<false, false, 16>(ga, st);
-      case 3: return launch256f<false, false, 32>(ga, st);
-      case 4: return launch256f<false, false, 64>(ga, st);
-      case 8: return launch256f<false, false, 8>(ga, st);
-      default: return launch256f<false, false, 9>(ga, st);
+      case 1: return launch256f<false, false, 1>(ga, walk, st);
+      case 2: return launch256f<false, false, 16>(ga, walk, st);
+      case 3: return launch256f<false, false, 32>(ga, walk, st);
+      case 4: return launch256f<false, false, 64>(ga, walk, st);
+      case 8: return launch256f<false, false, 8>(ga, walk, st);
+      default: return launch256f<false, false, 9>(ga, walk, st);
     }
   }
 #endif
   if (variant & 1) {
     switch (layout) {
-      case 0: return launch256f<false, false>(ga, st);
-      case 1: return launch256f<false, true>(ga, st);
-      default: return (ga.pad_ >> 8) ? launch256f<true, true, 0, true>(ga, st) : launch256f<true, true>(ga, st);
+      case 0: return launch256f<false, false>(ga, walk, st);
+      case 1: return launch256f<false, true>(ga, walk, st);
+      default: return (ga.pad_ >> 8) ? launch256f<true, true, 0, true>(ga, walk, st) : launch256f<true, true>(ga, walk, st);
     }
   }
   switch (layout) {
-    case 0: return launch256<false, false, false>(ga, st);
-    case 1: return launch256<false, true, false>(ga, st);
-    default: return launch256<true, true, false>(ga, st);
+    case 0: return launch256<false, false, false>(ga, walk, st);
+    case 1: return launch256<false, true, false>(ga, walk, st);
+    default: return launch256<true, true, false>(ga, walk, st);
   }
 }
+#undef G8_GROUP
+#undef G8_SB
+#undef DISPATCH_EPILOGUE

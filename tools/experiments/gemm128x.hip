@@ -204,9 +204,9 @@ __global__ __launch_bounds__(512, 2) void gemm128x_kernel(const GroupArgs ga) {
   // prologue: stages 0 and 1 of the first tile into ring slots 0 and 1
   unsigned sa_off = 0, sb_off = 0;                                               // ring slot of the stage being consumed
   unsigned a_dst = a_dst0 + 2 * X_A_BYTES, b_dst = b_dst0 + 2 * TILE2_BYTES;     // ring slot of the stage being requested (two ahead)
-  glds16_pair<0>(a_cur, va[0], va[1], a_dst0);
+  glds16_pair(a_cur, va[0], va[1], a_dst0);
   glds16_quad(b_cur, vb[0], vb[1], vb[2], vb[3], b_dst0);
-  glds16_pair<0>(a_cur + BK2, va[0], va[1], a_dst0 + X_A_BYTES);
+  glds16_pair(a_cur + BK2, va[0], va[1], a_dst0 + X_A_BYTES);
   glds16_quad(b_cur + b_kstep, vb[0], vb[1], vb[2], vb[3], b_dst0 + TILE2_BYTES);
   if (!(ABL & 2)) {
     // four stores of zeros into the first tile's last row block (overwritten by its real epilogue): the first step's wait then
