@@ -43,10 +43,11 @@ def test_gemm(st, layout, M, N, K, epi, sk):
     assert st.check_gemm(layout, M, N, K, epi, sk) < 6e-3
 
 
-@pytest.mark.parametrize("M", [768, 4096])
+@pytest.mark.parametrize("M", [768, 4096, 8192])
 def test_gemm_colsum_epilogue(st, M):
-    """EPI_COLSUM: the dgrad GEMM also accumulates its output's column sums (bias gradient of the producing layer); M = 4096
-    takes the two-pass fold of the workspace variant (32 workspace rows), 768 the single pass."""
+    """EPI_COLSUM: the dgrad GEMM also accumulates its output's column sums (bias gradient of the producing layer).  The workspace
+    variant leaves 2 * M / 128 rows here: 12 and 64 rows (M = 768, 4096) are folded in a single pass, 128 rows (M = 8192: more than
+    64 and a multiple of 16) by the two-pass fold every full-size step uses (tests/test_gpu_row_kernels.py has both on their own)."""
     from kbner import ops
     from kbner.lib import EPI_COLSUM, EPI_COLSUM_WS, EPI_DGELU, GEMM_NN
     g = torch.Generator(device="cpu").manual_seed(0)
