@@ -13,12 +13,20 @@
 // the probabilities feed the next MFMA as a B operand straight from registers; k-strided operands
 // (V^T, K^T, Q^T, dO^T) come from the same row-major panels via ds_read_b64_tr_b16.
 //
-//   attn_fwd     grid (S/128, A, B): panels K,V ; stationary Q        -> O [M,H], lse [B,A,S]
-//   attn_bwd_dq  grid (S/128, A, B): panels K,V ; stationary Q,dO     -> dQ
-//   attn_bwd_dkv grid (S/128, A, B): panels Q,dO; stationary K,V      -> dK, dV
+// Six kernel templates, two per task: 16 stationary rows per wave and pass, or 32 (two row blocks share every LDS fragment
+// read: half the LDS bytes per flop) where a workgroup's row tile rpw gives each of its 8 waves whole 32-row passes.
+//
+//   attn_fwd_kernel      grid (S/rpw, A, B), or one workgroup per CU walking whole heads (PERSIST): panels K,V ; stationary Q
+//   attn_fwd32_kernel    the same with 32 rows per pass, keys in two halves (no dropout, S >= 192)         -> O [M,H], lse [B,A,S]
+//   attn_bwd_dq_kernel   grid (S/rpw, A, B): panels K,V ; stationary Q,dO                                 -> dQ, D [B,A,S]
+//   attn_bwd_dq2_kernel  the same with 32 rows per pass
+//   attn_bwd_dkv_kernel  grid (S/rpw, A, B): panels Q,dO; stationary K,V                                  -> dK, dV
+//   attn_bwd_dkv2_kernel the same with 32 rows per pass
 // (backward recomputes S and dP once per kernel: 7 matmuls instead of 5, no atomics, no LDS
 // round trip of computed tiles.)  qkv / dqkv are token-major [M, 3H] (Q | K | V), head h at
 // column h*64, exactly what the fused QKV GEMM produces / consumes: no permute kernels.
+// What the kernels share -- the LDS layout, fragment reads, MFMA tile macros, dropout keys, epilogues -- is in attn_common.h;
+// which kernel a shape runs is decided at the bottom of this file (pick_rpw, launch_attn_fwd, launch_attn_bwd).
 #include "common.h"
 #include <cstdlib>
 
@@ -45,10 +53,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
                                                           int nitems) {
   constexpr int S = NKB * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sK = smem;
-  unsigned char* sV = smem + AT_MAXS * 128;
-  float* sMask = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  uint32_t* sCk = reinterpret_cast<uint32_t*>(sMask + AT_MAXS);
+  unsigned char *sK = at_panel(smem, 0), *sV = at_panel(smem, 1);
+  float* sMask = at_row<float>(smem, 0);
+  uint32_t* sCk = at_row<uint32_t>(smem, 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qt = PERSIST ? 0 : blockIdx.x;
@@ -80,7 +87,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
   stage_panel(qkv + (size_t)b * S * ld + h * AT_D + H, ld, S, sK, wid, lane);
   stage_panel(qkv + (size_t)b * S * ld + h * AT_D + 2 * H, ld, S, sV, wid, lane);
   const int g = lane >> 4, li = lane & 15;
-  // per-lane LDS bases (see kc_frag / tr_frag): K rows f*16 + li -> + f*2048 ; V rows kc*32 + g*4 + (li>>2) -> + kc*4096
+  // per-lane LDS bases (as panel_bases() computes them): K rows f*16 + li -> + f*2048 ; V rows kc*32 + g*4 + (li>>2) -> + kc*4096
   const unsigned char* kb0 = sK + li * 128 + (((0 * 4 + g) ^ kc_swz(li)) << 4);
   const unsigned char* kb1 = sK + li * 128 + (((1 * 4 + g) ^ kc_swz(li)) << 4);
   const int vrow = g * 4 + (li >> 2);
@@ -114,8 +121,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int f = 0; f < NKB; ++f) {
           f4v a = (f4v){0.f, 0.f, 0.f, 0.f};
-          a = MFMA(__builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb0 + f * 2048)), qf0, a);
-          a = MFMA(__builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb1 + f * 2048)), qf1, a);
+          a = MFMA(kc_at(kb0, f * 2048), qf0, a);
+          a = MFMA(kc_at(kb1, f * 2048), qf1, a);
           // the row maximum is taken on the RAW sums (scale2 > 0 commutes with max): two v_max3 per fragment, no multiply
           mx = fmaxf(fmaxf(mx, a[0]), a[1]);
           mx = fmaxf(fmaxf(mx, a[2]), a[3]);
@@ -125,8 +132,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int f = 0; f < NKB; ++f) {
           f4v a = *reinterpret_cast<const f4v*>(sMask + f * 16 + g * 4);   // accumulators start at mask / scale
-          a = MFMA(__builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb0 + f * 2048)), qf0, a);
-          a = MFMA(__builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb1 + f * 2048)), qf1, a);
+          a = MFMA(kc_at(kb0, f * 2048), qf0, a);
+          a = MFMA(kc_at(kb1, f * 2048), qf1, a);
           mx = fmaxf(fmaxf(mx, a[0]), a[1]);
           mx = fmaxf(fmaxf(mx, a[2]), a[3]);
           st[f] = a;
@@ -145,11 +152,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
         a[3] = __builtin_amdgcn_exp2f(a[3] * scale2 + nmx);
         if (DROP) {
           sum += (a[0] + a[1]) + (a[2] + a[3]);  // normaliser of the UNdropped softmax
-          const uint4 ck = *reinterpret_cast<const uint4*>(sCk + f * 16 + g * 4);
-          a[0] = drop_keep(rk, ck.x, drop_thresh) ? a[0] : 0.0f;
-          a[1] = drop_keep(rk, ck.y, drop_thresh) ? a[1] : 0.0f;
-          a[2] = drop_keep(rk, ck.z, drop_thresh) ? a[2] : 0.0f;
-          a[3] = drop_keep(rk, ck.w, drop_thresh) ? a[3] : 0.0f;
+          a = drop_zero4(a, rk, sCk + f * 16 + g * 4, drop_thresh);
         }
         st[f] = a;
       }
@@ -183,31 +186,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const bf16_t* __restri
         const bf16x8 pb = pack_b(st[2 * kc], st[2 * kc + 1]);
         if (!DROP) osum = MFMA(ones, pb, osum);
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const unsigned char* a = vb[db] + kc * 4096;
-          const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a));
-          const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a + 16 * 128));
-          s8v v;
-          v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-          v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-          o[db] = MFMA(__builtin_bit_cast(bf16x8, v), pb, o[db]);
-        }
+        for (int db = 0; db < 4; ++db) o[db] = MFMA(tr_at(vb[db], kc * 4096), pb, o[db]);
       }
-      // O^T fragment: lane holds O[q0+li][db*16 + g*4 .. +3]
       if (!DROP) sum = osum[0];  // every row of ones.P^T holds the column (= query) sums
-      const float inv = dscale / sum;
-      bf16_t* orow = ctx + (size_t)(b * S + q0 + li) * H + h * AT_D;
-      uint32_t res[4];
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        uint2 u;
-        u.x = pack2bf_res8(o[db][0] * inv, o[db][1] * inv, res[db], false);
-        u.y = pack2bf_res8(o[db][2] * inv, o[db][3] * inv, res[db], true);
-        *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;
-      }
-      if (ctx_lo)   // O - bf16(O), one byte per element, 16 B per lane and 16-row block (at_res_block): see kbner_attn_bwd
-        *reinterpret_cast<uint4*>(at_res_block(ctx_lo, b, A, h, S, q0) + lane * 16) = make_uint4(res[0], res[1], res[2], res[3]);
-      if (g == 0) lse[((size_t)b * A + h) * S + q0 + li] = (mx + __log2f(sum)) * 0.6931471805599453f;
+      AT_STORE_CTX(o, dscale / sum, mx, sum, q0)
     }
   }
   if (!has_next) break;
@@ -238,10 +220,9 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
   constexpr int S = NKB * 16;
   constexpr int NH = NKB / NP;  // 16-key fragments per part (NP parts of the key axis, joined by NP - 1 online-softmax steps per row)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sK = smem;
-  unsigned char* sV = smem + AT_MAXS * 128;
-  float* sMask = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  uint32_t* sCk = reinterpret_cast<uint32_t*>(sMask + AT_MAXS);
+  unsigned char *sK = at_panel(smem, 0), *sV = at_panel(smem, 1);
+  float* sMask = at_row<float>(smem, 0);
+  uint32_t* sCk = at_row<uint32_t>(smem, 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qt = PERSIST ? 0 : blockIdx.x;
@@ -321,8 +302,8 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
         if (plain) {
 #pragma unroll
           for (int f = 0; f < NH; ++f) {
-            const bf16x8 k0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb0 + (half * NH + f) * 2048));
-            const bf16x8 k1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb1 + (half * NH + f) * 2048));
+            const bf16x8 k0 = kc_at(kb0, (half * NH + f) * 2048);
+            const bf16x8 k1 = kc_at(kb1, (half * NH + f) * 2048);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
               f4v a = (f4v){0.f, 0.f, 0.f, 0.f};
@@ -336,8 +317,8 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
         } else {
 #pragma unroll
           for (int f = 0; f < NH; ++f) {
-            const bf16x8 k0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb0 + (half * NH + f) * 2048));
-            const bf16x8 k1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(kb1 + (half * NH + f) * 2048));
+            const bf16x8 k0 = kc_at(kb0, (half * NH + f) * 2048);
+            const bf16x8 k1 = kc_at(kb1, (half * NH + f) * 2048);
             const f4v mk = *reinterpret_cast<const f4v*>(sMask + (half * NH + f) * 16 + g * 4);   // mask / scale
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -377,11 +358,7 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
               a[3] = __builtin_amdgcn_exp2f(a[3] * scale2 + nmx);
               if (DROP) {
                 sum[j] += (a[0] + a[1]) + (a[2] + a[3]);   // normaliser of the UNdropped softmax (reduced over g at the end)
-                const uint4 ck = *reinterpret_cast<const uint4*>(sCk + (half * NH + f) * 16 + g * 4);
-                a[0] = drop_keep(rk[j], ck.x, drop_thresh) ? a[0] : 0.0f;
-                a[1] = drop_keep(rk[j], ck.y, drop_thresh) ? a[1] : 0.0f;
-                a[2] = drop_keep(rk[j], ck.z, drop_thresh) ? a[2] : 0.0f;
-                a[3] = drop_keep(rk[j], ck.w, drop_thresh) ? a[3] : 0.0f;
+                a = drop_zero4(a, rk[j], sCk + (half * NH + f) * 16 + g * 4, drop_thresh);
               }
               e[t] = a;
             }
@@ -413,13 +390,7 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
           }
 #pragma unroll
           for (int db = 0; db < 4; ++db) {
-            const unsigned char* a = vb[db] + (half * (NH / 2) + kc) * 4096;
-            const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a));
-            const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a + 16 * 128));
-            s8v v;
-            v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-            v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-            const bf16x8 vf = __builtin_bit_cast(bf16x8, v);
+            const bf16x8 vf = tr_at(vb[db], (half * (NH / 2) + kc) * 4096);
             o[0][db] = MFMA(vf, pb0, o[0][db]);
             o[1][db] = MFMA(vf, pb1, o[1][db]);
           }
@@ -430,20 +401,7 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(const bf16_t* __restric
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const float sm = DROP ? group4_sum(sum[j]) : osum[j][0];
-        const float inv = dscale / sm;
-        bf16_t* orow = ctx + (size_t)(b * S + q0 + j * 16 + li) * H + h * AT_D;
-        uint32_t res[4];
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          uint2 u;
-          u.x = pack2bf_res8(o[j][db][0] * inv, o[j][db][1] * inv, res[db], false);
-          u.y = pack2bf_res8(o[j][db][2] * inv, o[j][db][3] * inv, res[db], true);
-          *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;
-        }
-        if (ctx_lo)   // O - bf16(O), one byte per element, 16 B per lane and 16-row block (at_res_block): see kbner_attn_bwd
-          *reinterpret_cast<uint4*>(at_res_block(ctx_lo, b, A, h, S, q0 + j * 16) + lane * 16) =
-              make_uint4(res[0], res[1], res[2], res[3]);
-        if (g == 0) lse[((size_t)b * A + h) * S + q0 + j * 16 + li] = (m[j] * scale2 + __log2f(sm)) * 0.6931471805599453f;
+        AT_STORE_CTX(o[j], dscale / sm, m[j] * scale2, sm, q0 + j * 16)
       }
     }
   }
@@ -493,18 +451,17 @@ static __device__ __forceinline__ void flush_colsum(f4v (&acc)[4], float (*red)[
 // It also produces D[b,h,q] = rowdot(dO, O) (the softmax-backward correction) for its own queries from the dO / O
 // fragments it already needs, and writes it for the dK/dV kernel that runs next: no separate row-dot pass.
 template <bool DROP, bool RES>
-__global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+__global__ __launch_bounds__(AT_NW * 64) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                              const bf16_t* __restrict__ ctx, const uint8_t* __restrict__ ctx_lo,
                                                              const float* __restrict__ maskbias, const float* __restrict__ lse,
                                                              float* __restrict__ Dv, bf16_t* __restrict__ dqkv, int S,
                                                              int H, int A, float scale, int rpw, uint32_t drop_seed,
                                                              uint32_t drop_thresh, float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[AT_NWB][64];
-  unsigned char* sK = smem;
-  unsigned char* sV = smem + AT_MAXS * 128;
-  float* sMask = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  uint32_t* sCk = reinterpret_cast<uint32_t*>(sMask + AT_MAXS);
+  __shared__ float red[AT_NW][64];
+  unsigned char *sK = at_panel(smem, 0), *sV = at_panel(smem, 1);
+  float* sMask = at_row<float>(smem, 0);
+  uint32_t* sCk = at_row<uint32_t>(smem, 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -515,9 +472,9 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
   f4v bsum[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsum[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  stage_panel<AT_NWB>(base + H, ld, S, sK, wid, lane);
-  stage_panel<AT_NWB>(base + 2 * H, ld, S, sV, wid, lane);
-  for (int i = tid; i < S; i += AT_NWB * 64) {
+  stage_panel(base + H, ld, S, sK, wid, lane);
+  stage_panel(base + 2 * H, ld, S, sV, wid, lane);
+  for (int i = tid; i < S; i += AT_NW * 64) {
     sMask[i] = maskbias[(size_t)b * S + i] * 1.4426950408889634f;
     if (DROP) sCk[i] = drop_colkey(drop_seed, bhS + (uint32_t)i);
   }
@@ -530,8 +487,8 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
   const bf16_t* dob = dctx + (size_t)b * S * H + h * AT_D;
   const bf16_t* ob = ctx + (size_t)b * S * H + h * AT_D;
 #pragma unroll 1
-  for (int pass = 0; pass < rpw / (16 * AT_NWB); ++pass) {
-    const int q0 = qt * rpw + wid * (rpw / AT_NWB) + pass * 16;
+  for (int pass = 0; pass < rpw / (16 * AT_NW); ++pass) {
+    const int q0 = qt * rpw + wid * (rpw / AT_NW) + pass * 16;
     if (q0 >= S) break;
     const bf16x8 qf0 = glb_frag(base, ld, q0, 0, lane);
     const bf16x8 qf1 = glb_frag(base, ld, q0, 1, lane);
@@ -539,13 +496,11 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
     const bf16x8 do1 = glb_frag(dob, H, q0, 1, lane);
     const size_t sidx = ((size_t)b * A + h) * S + q0 + li;
     const float l_q = lse[sidx] * 1.4426950408889634f;  // log2 domain
-    // D = sum_d dO[q,d] O[q,d]: each lane group g holds 16 of the 64 d of row q0+li in its two fragments
+    // D = sum_d dO[q,d] O[q,d]
     const bf16x8 of0 = glb_frag(ob, H, q0, 0, lane), of1 = glb_frag(ob, H, q0, 1, lane);
     uint32_t rw[4];
     if (RES) res_words(at_res_block(ctx_lo, b, A, h, S, q0), lane, rw);
-    float d_part = dot8(do0, of0) + dot8(do1, of1);
-    if (RES) d_part += res_dot16(do0, do1, rw);   // the residual of O
-    const float d_true = group4_sum(d_part);
+    const float d_true = rowdot_do_o<RES>(do0, do1, of0, of1, rw);
     if (g == 0) Dv[sidx] = d_true;
     // dropout: dS = (1 / (1-p)) P (m dP - (1-p) D) -- the 1 / (1-p) leaves through the final dQ scale (see attn_bwd_dq2_kernel)
     const float d_q = DROP ? d_true * (1.0f / dscale) : d_true;
@@ -555,15 +510,9 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
     for (int db = 0; db < 4; ++db) dq[db] = (f4v){0.f, 0.f, 0.f, 0.f};
     // two-stage software pipeline: the 8 score / dP MFMAs of chunk kc+1 are issued before the softmax VALU work
     // of chunk kc, so the matrix pipe runs under the exp2 / multiply stream of the same wave
-#define DQ_SP(S0, S1, P0, P1, CO)                 \
-  S0 = MFMA(kc_at(pK.kc[0], (CO)), qf0, zero4);          \
-  S0 = MFMA(kc_at(pK.kc[1], (CO)), qf1, S0);             \
-  S1 = MFMA(kc_at(pK.kc[0], (CO) + 2048), qf0, zero4);   \
-  S1 = MFMA(kc_at(pK.kc[1], (CO) + 2048), qf1, S1);      \
-  P0 = MFMA(kc_at(pV.kc[0], (CO)), do0, pinit);          \
-  P0 = MFMA(kc_at(pV.kc[1], (CO)), do1, P0);             \
-  P1 = MFMA(kc_at(pV.kc[0], (CO) + 2048), do0, pinit);   \
-  P1 = MFMA(kc_at(pV.kc[1], (CO) + 2048), do1, P1)
+#define DQ_SP(S0, S1, P0, P1, CO)                           \
+  AT_CHUNK_MFMA(S0, S1, pK, CO, qf0, qf1, zero4, zero4);  \
+  AT_CHUNK_MFMA(P0, P1, pV, CO, do0, do1, pinit, pinit)
     const f4v zero4 = (f4v){0.f, 0.f, 0.f, 0.f};
     // without dropout the dP accumulators START at -D (one query per lane): dS = P * (dP - D) loses its subtraction
     const f4v pinit = (f4v){-d_q, -d_q, -d_q, -d_q};
@@ -583,10 +532,8 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
       f4v ds0, ds1;
       uint32_t ck0[4] = {0u, 0u, 0u, 0u}, ck1[4] = {0u, 0u, 0u, 0u};
       if (DROP) {
-        const uint4 c0 = *reinterpret_cast<const uint4*>(sCk + kc * 32 + g * 4);
-        const uint4 c1 = *reinterpret_cast<const uint4*>(sCk + kc * 32 + 16 + g * 4);
-        ck0[0] = c0.x; ck0[1] = c0.y; ck0[2] = c0.z; ck0[3] = c0.w;
-        ck1[0] = c1.x; ck1[1] = c1.y; ck1[2] = c1.z; ck1[3] = c1.w;
+        load_keys4(sCk + kc * 32 + g * 4, ck0);
+        load_keys4(sCk + kc * 32 + 16 + g * 4, ck1);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -609,48 +556,43 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dq_kernel(const bf16_t* 
     bf16_t* orow = dqkv + (size_t)(b * S + q0 + li) * ld + h * AT_D;
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
-      uint2 u;
       const float os = scale * dscale;
-      u.x = pack2bf(dq[db][0] * os, dq[db][1] * os);
-      u.y = pack2bf(dq[db][2] * os, dq[db][3] * os);
-      *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;
+      AT_STORE_SCALED(dq, os, orow, db)
       bsum[db] += dq[db] * os;
     }
   }
-  if (dbias != nullptr) flush_colsum<AT_NWB>(bsum, red, dbias + h * AT_D, wid, lane, tid);
+  if (dbias != nullptr) flush_colsum<AT_NW>(bsum, red, dbias + h * AT_D, wid, lane, tid);
 }
 
 // ------------------------------------------------------------------------------------------
 // backward: dK, dV   (owner = key rows; panels Q, dO)
 // ------------------------------------------------------------------------------------------
 template <bool DROP>
-__global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+__global__ __launch_bounds__(AT_NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                               const float* __restrict__ maskbias, const float* __restrict__ lse,
                                                               const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, int S,
                                                               int H, int A, float scale, int rpw, uint32_t drop_seed,
                                                               uint32_t drop_thresh, float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[AT_NWB][64];
+  __shared__ float red[AT_NW][64];
   f4v bsk[4], bsv[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsk[db] = bsv[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  unsigned char* sQ = smem;
-  unsigned char* sO = smem + AT_MAXS * 128;
-  float* sL = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  float* sD = sL + AT_MAXS;
-  uint32_t* sRk = reinterpret_cast<uint32_t*>(sD + AT_MAXS);  // dropout row keys of the head's queries
+  unsigned char *sQ = at_panel(smem, 0), *sO = at_panel(smem, 1);
+  float *sL = at_row<float>(smem, 0), *sD = at_row<float>(smem, 1);
+  uint32_t* sRk = at_row<uint32_t>(smem, 2);   // dropout row keys of the head's queries
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int ld = 3 * H;
   const bf16_t* base = qkv + (size_t)b * S * ld + h * AT_D;
   const bf16_t* dob = dctx + (size_t)b * S * H + h * AT_D;
-  stage_panel<AT_NWB>(base, ld, S, sQ, wid, lane);
-  stage_panel<AT_NWB>(dob, H, S, sO, wid, lane);
+  stage_panel(base, ld, S, sQ, wid, lane);
+  stage_panel(dob, H, S, sO, wid, lane);
   const size_t sbase = ((size_t)b * A + h) * S;
   const uint32_t bhS = (uint32_t)sbase;
   const float dscale = DROP ? drop_scale(drop_thresh) : 1.0f;
-  for (int i = tid; i < S; i += AT_NWB * 64) {
+  for (int i = tid; i < S; i += AT_NW * 64) {
     sL[i] = lse[sbase + i] * 1.4426950408889634f;  // log2 domain
     sD[i] = -Dv[sbase + i] * (1.0f / dscale);  // the dP accumulators start at -(1-p) D (= -D without dropout)
     if (DROP) sRk[i] = drop_rowkey(drop_seed, bhS + (uint32_t)i);
@@ -662,8 +604,8 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dkv_kernel(const bf16_t*
   const float scale2 = scale * 1.4426950408889634f;
   const PanelBases pQ = panel_bases(sQ, lane), pO = panel_bases(sO, lane);
 #pragma unroll 1
-  for (int pass = 0; pass < rpw / (16 * AT_NWB); ++pass) {
-    const int k0 = kt * rpw + wid * (rpw / AT_NWB) + pass * 16;
+  for (int pass = 0; pass < rpw / (16 * AT_NW); ++pass) {
+    const int k0 = kt * rpw + wid * (rpw / AT_NW) + pass * 16;
     if (k0 >= S) break;
     const bf16x8 kf0 = glb_frag(base + H, ld, k0, 0, lane);
     const bf16x8 kf1 = glb_frag(base + H, ld, k0, 1, lane);
@@ -678,15 +620,9 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dkv_kernel(const bf16_t*
       dv[db] = (f4v){0.f, 0.f, 0.f, 0.f};
     }
 #define nd_at(CO, off) (*reinterpret_cast<const f4v*>(sD + ((CO) >> 7) + (off) + g * 4))
-#define DKV_SP(S0, S1, P0, P1, CO)                \
-  S0 = MFMA(kc_at(pQ.kc[0], (CO)), kf0, zero4);          \
-  S0 = MFMA(kc_at(pQ.kc[1], (CO)), kf1, S0);             \
-  S1 = MFMA(kc_at(pQ.kc[0], (CO) + 2048), kf0, zero4);   \
-  S1 = MFMA(kc_at(pQ.kc[1], (CO) + 2048), kf1, S1);      \
-  P0 = MFMA(kc_at(pO.kc[0], (CO)), vf0, nd_at((CO), 0));  \
-  P0 = MFMA(kc_at(pO.kc[1], (CO)), vf1, P0);             \
-  P1 = MFMA(kc_at(pO.kc[0], (CO) + 2048), vf0, nd_at((CO), 16)); \
-  P1 = MFMA(kc_at(pO.kc[1], (CO) + 2048), vf1, P1)
+#define DKV_SP(S0, S1, P0, P1, CO)                          \
+  AT_CHUNK_MFMA(S0, S1, pQ, CO, kf0, kf1, zero4, zero4);  \
+  AT_CHUNK_MFMA(P0, P1, pO, CO, vf0, vf1, nd_at((CO), 0), nd_at((CO), 16))
     const f4v zero4 = (f4v){0.f, 0.f, 0.f, 0.f};
     f4v s0, s1, p0, p1;
     DKV_SP(s0, s1, p0, p1, 0);
@@ -705,10 +641,8 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dkv_kernel(const bf16_t*
       f4v pr0, pr1, ds0, ds1;
       uint32_t rk0[4] = {0u, 0u, 0u, 0u}, rk1[4] = {0u, 0u, 0u, 0u};
       if (DROP) {
-        const uint4 c0 = *reinterpret_cast<const uint4*>(sRk + qc * 32 + g * 4);
-        const uint4 c1 = *reinterpret_cast<const uint4*>(sRk + qc * 32 + 16 + g * 4);
-        rk0[0] = c0.x; rk0[1] = c0.y; rk0[2] = c0.z; rk0[3] = c0.w;
-        rk1[0] = c1.x; rk1[1] = c1.y; rk1[2] = c1.z; rk1[3] = c1.w;
+        load_keys4(sRk + qc * 32 + g * 4, rk0);
+        load_keys4(sRk + qc * 32 + 16 + g * 4, rk1);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -742,22 +676,16 @@ __global__ __launch_bounds__(AT_NWB * 64) void attn_bwd_dkv_kernel(const bf16_t*
     bf16_t* vrow = krow + H;
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
-      uint2 u;
       const float ks = scale * dscale;
-      u.x = pack2bf(dk[db][0] * ks, dk[db][1] * ks);
-      u.y = pack2bf(dk[db][2] * ks, dk[db][3] * ks);
-      *reinterpret_cast<uint2*>(krow + db * 16 + g * 4) = u;
-      uint2 w;
-      w.x = pack2bf(dv[db][0] * dscale, dv[db][1] * dscale);
-      w.y = pack2bf(dv[db][2] * dscale, dv[db][3] * dscale);
-      *reinterpret_cast<uint2*>(vrow + db * 16 + g * 4) = w;
+      AT_STORE_SCALED(dk, ks, krow, db)
+      AT_STORE_SCALED(dv, dscale, vrow, db)
       bsk[db] += dk[db] * ks;
       bsv[db] += dv[db] * dscale;
     }
   }
   if (dbias != nullptr) {
-    flush_colsum<AT_NWB>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
-    flush_colsum<AT_NWB>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
   }
 }
 
@@ -818,12 +746,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
                                                           bf16_t* __restrict__ dqkv, int S, int H, int A, float scale, int rpw,
                                                           uint32_t drop_seed, uint32_t drop_thresh, float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8][64];
+  __shared__ float red[AT_NW][64];
   __shared__ int sKlen[2];
-  unsigned char* sK = smem;
-  unsigned char* sV = smem + AT_MAXS * 128;
-  float* sMask = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  uint32_t* sCk = reinterpret_cast<uint32_t*>(sMask + AT_MAXS);
+  unsigned char *sK = at_panel(smem, 0), *sV = at_panel(smem, 1);
+  float* sMask = at_row<float>(smem, 0);
+  uint32_t* sCk = at_row<uint32_t>(smem, 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -834,8 +761,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
   f4v bsum[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsum[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  stage_panel<8>(base + H, ld, S, sK, wid, lane);
-  stage_panel<8>(base + 2 * H, ld, S, sV, wid, lane);
+  stage_panel(base + H, ld, S, sK, wid, lane);
+  stage_panel(base + 2 * H, ld, S, sV, wid, lane);
   int nfree;
   const int klen = stage_mask_klen<512>(maskbias, (size_t)b * S, S, 1.0f / scale, sMask, sKlen, tid, nfree);
   if (DROP)
@@ -879,10 +806,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
       const int qj = q0 + j * 16;
       const size_t sidx = ((size_t)b * A + h) * S + qj + li;
       l_q[j] = -lse_q[j] / scale;   // accumulator init of the score MFMAs: exp2(scale2 * (q.k + mask/scale - lse/scale))
-      float d_part = dot8(dof[j][0], of[j][0]) + dot8(dof[j][1], of[j][1]);
-      if (RES)   // the residual O - bf16(O) the forward kept: D to ~12 bits of O (see kbner_attn_bwd)
-        d_part += res_dot16(dof[j][0], dof[j][1], rw[j]);
-      d_q[j] = group4_sum(d_part);
+      d_q[j] = rowdot_do_o<RES>(dof[j][0], dof[j][1], of[j][0], of[j][1], rw[j]);
       if (g == 0) Dv[sidx] = d_q[j];
       // with dropout dS = P (m dP / (1-p) - D) = (1 / (1-p)) P (m dP - (1-p) D): the 1 / (1-p) moves to the final dQ scale and the
       // accumulators of dP start at -(1-p) D as they start at -D without dropout (a dropped element keeps that start value)
@@ -904,8 +828,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
       const unsigned char* bt[4] = {pK.tr[0] + kc * 4096, pK.tr[1] + kc * 4096, pK.tr[2] + kc * 4096, pK.tr[3] + kc * 4096};
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        constexpr int dummy = 0;
-        (void)dummy;
         const int co = u * 4096;
         const bool masked = (kc + u) >= nfree;   // wave-uniform
         const bf16x8 k00 = kc_at(bk0, co), k01 = kc_at(bk1, co);
@@ -914,10 +836,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
         const bf16x8 v10 = kc_at(bv0, co + 2048), v11 = kc_at(bv1, co + 2048);
         uint32_t ck0[4] = {0u, 0u, 0u, 0u}, ck1[4] = {0u, 0u, 0u, 0u};
         if (DROP) {
-          const uint4 c0 = *reinterpret_cast<const uint4*>(sCk + (kc + u) * 32 + g * 4);
-          const uint4 c1 = *reinterpret_cast<const uint4*>(sCk + (kc + u) * 32 + 16 + g * 4);
-          ck0[0] = c0.x; ck0[1] = c0.y; ck0[2] = c0.z; ck0[3] = c0.w;
-          ck1[0] = c1.x; ck1[1] = c1.y; ck1[2] = c1.z; ck1[3] = c1.w;
+          load_keys4(sCk + (kc + u) * 32 + g * 4, ck0);
+          load_keys4(sCk + (kc + u) * 32 + 16 + g * 4, ck1);
         }
         // S^T and dP^T tiles [key, query] (lane: keys g*4 + r of each 16-key fragment, query li) for both row blocks
         f4v s0[2], s1[2], p0[2], p1[2];
@@ -925,14 +845,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
         for (int j = 0; j < 2; ++j) {
           const f4v sinit = (f4v){l_q[j], l_q[j], l_q[j], l_q[j]};
           const f4v pinit = (f4v){-d_q[j], -d_q[j], -d_q[j], -d_q[j]};
-          s0[j] = MFMA(k00, qf[j][0], sinit);
-          s0[j] = MFMA(k01, qf[j][1], s0[j]);
-          s1[j] = MFMA(k10, qf[j][0], sinit);
-          s1[j] = MFMA(k11, qf[j][1], s1[j]);
-          p0[j] = MFMA(v00, dof[j][0], pinit);
-          p0[j] = MFMA(v01, dof[j][1], p0[j]);
-          p1[j] = MFMA(v10, dof[j][0], pinit);
-          p1[j] = MFMA(v11, dof[j][1], p1[j]);
+          AT_MFMA2(s0[j], k00, k01, qf[j][0], qf[j][1], sinit);
+          AT_MFMA2(s1[j], k10, k11, qf[j][0], qf[j][1], sinit);
+          AT_MFMA2(p0[j], v00, v01, dof[j][0], dof[j][1], pinit);
+          AT_MFMA2(p1[j], v10, v11, dof[j][0], dof[j][1], pinit);
         }
         if (masked) {
           const f4v m0 = *reinterpret_cast<const f4v*>(sMask + (kc + u) * 32 + g * 4);
@@ -974,15 +890,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(const bf16_t* __restr
       bf16_t* orow = dqkv + (size_t)(b * S + q0 + j * 16 + li) * ld + h * AT_D;
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        uint2 u;
-        u.x = pack2bf(dq[j][db][0] * oscale, dq[j][db][1] * oscale);
-        u.y = pack2bf(dq[j][db][2] * oscale, dq[j][db][3] * oscale);
-        *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;
+        AT_STORE_SCALED(dq[j], oscale, orow, db)
         bsum[db] += dq[j][db] * oscale;
       }
     }
   }
-  if (dbias != nullptr) flush_colsum<8>(bsum, red, dbias + h * AT_D, wid, lane, tid);
+  if (dbias != nullptr) flush_colsum<AT_NW>(bsum, red, dbias + h * AT_D, wid, lane, tid);
 }
 
 template <bool DROP>
@@ -992,23 +905,21 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv2_kernel(const bf16_t* __rest
                                                            int H, int A, float scale, int rpw, uint32_t drop_seed,
                                                            uint32_t drop_thresh, float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8][64];
+  __shared__ float red[AT_NW][64];
   f4v bsk[4], bsv[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsk[db] = bsv[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  unsigned char* sQ = smem;
-  unsigned char* sO = smem + AT_MAXS * 128;
-  float* sL = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  float* sD = sL + AT_MAXS;
-  uint32_t* sRk = reinterpret_cast<uint32_t*>(sD + AT_MAXS);
+  unsigned char *sQ = at_panel(smem, 0), *sO = at_panel(smem, 1);
+  float *sL = at_row<float>(smem, 0), *sD = at_row<float>(smem, 1);
+  uint32_t* sRk = at_row<uint32_t>(smem, 2);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int ld = 3 * H;
   const bf16_t* base = qkv + (size_t)b * S * ld + h * AT_D;
   const bf16_t* dob = dctx + (size_t)b * S * H + h * AT_D;
-  stage_panel<8>(base, ld, S, sQ, wid, lane);
-  stage_panel<8>(dob, H, S, sO, wid, lane);
+  stage_panel(base, ld, S, sQ, wid, lane);
+  stage_panel(dob, H, S, sO, wid, lane);
   const size_t sbase = ((size_t)b * A + h) * S;
   const uint32_t bhS = (uint32_t)sbase;
   const float dscale = DROP ? drop_scale(drop_thresh) : 1.0f;
@@ -1072,23 +983,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv2_kernel(const bf16_t* __rest
         const f4v nd1 = *reinterpret_cast<const f4v*>(pd + u * 32 + 16);
         uint32_t rk0[4] = {0u, 0u, 0u, 0u}, rk1[4] = {0u, 0u, 0u, 0u};
         if (DROP) {
-          const uint4 c0 = *reinterpret_cast<const uint4*>(prk + u * 32);
-          const uint4 c1 = *reinterpret_cast<const uint4*>(prk + u * 32 + 16);
-          rk0[0] = c0.x; rk0[1] = c0.y; rk0[2] = c0.z; rk0[3] = c0.w;
-          rk1[0] = c1.x; rk1[1] = c1.y; rk1[2] = c1.z; rk1[3] = c1.w;
+          load_keys4(prk + u * 32, rk0);
+          load_keys4(prk + u * 32 + 16, rk1);
         }
         // S and dP tiles [query, key]: lane holds queries (qc+u)*32 + f*16 + g*4 + r, key k0 + j*16 + li
         f4v s0[2], s1[2], p0[2], p1[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          s0[j] = MFMA(q00, kf[j][0], sl0);
-          s0[j] = MFMA(q01, kf[j][1], s0[j]);
-          s1[j] = MFMA(q10, kf[j][0], sl1);
-          s1[j] = MFMA(q11, kf[j][1], s1[j]);
-          p0[j] = MFMA(o00, vf[j][0], nd0);
-          p0[j] = MFMA(o01, vf[j][1], p0[j]);
-          p1[j] = MFMA(o10, vf[j][0], nd1);
-          p1[j] = MFMA(o11, vf[j][1], p1[j]);
+          AT_MFMA2(s0[j], q00, q01, kf[j][0], kf[j][1], sl0);
+          AT_MFMA2(s1[j], q10, q11, kf[j][0], kf[j][1], sl1);
+          AT_MFMA2(p0[j], o00, o01, vf[j][0], vf[j][1], nd0);
+          AT_MFMA2(p1[j], o10, o11, vf[j][0], vf[j][1], nd1);
         }
         if (masked) {
 #pragma unroll
@@ -1138,23 +1043,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv2_kernel(const bf16_t* __rest
       bf16_t* vrow = krow + H;
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        uint2 u;
         const float ks = scale * dscale;
-        u.x = pack2bf(dk[j][db][0] * ks, dk[j][db][1] * ks);
-        u.y = pack2bf(dk[j][db][2] * ks, dk[j][db][3] * ks);
-        *reinterpret_cast<uint2*>(krow + db * 16 + g * 4) = u;
-        uint2 w;
-        w.x = pack2bf(dv[j][db][0] * dscale, dv[j][db][1] * dscale);
-        w.y = pack2bf(dv[j][db][2] * dscale, dv[j][db][3] * dscale);
-        *reinterpret_cast<uint2*>(vrow + db * 16 + g * 4) = w;
+        AT_STORE_SCALED(dk[j], ks, krow, db)
+        AT_STORE_SCALED(dv[j], dscale, vrow, db)
         bsk[db] += dk[j][db] * ks;
         bsv[db] += dv[j][db] * dscale;
       }
     }
   }
   if (dbias != nullptr) {
-    flush_colsum<8>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
-    flush_colsum<8>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
   }
 }
 
@@ -1162,7 +1061,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv2_kernel(const bf16_t* __rest
 #include "attn_bwd3.h"   // tools/experiments/: round 5's software-pipelined backward stream (bit-identical, measured slower)
 #endif
 
-#define AT_LDS_BYTES (2 * AT_MAXS * 128 + 3 * AT_MAXS * 4)
 #ifndef KBNER_ATTN_PARTS
 #define KBNER_ATTN_PARTS 2   // key-axis parts of the 32-row forward kernel (4, for S % 128 == 0, measured slower: 263-268 vs 247-251 us)
 #endif
@@ -1175,57 +1073,56 @@ static inline int pick_rpw(int B, int S, int A) {
   return rpw;
 }
 
-
-template <int NKB, bool DROP>
-static int launch_attn_fwd2(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, uint8_t* ctx_lo, float* lse, int B, int H, int A, int rpw,
-                            uint32_t seed, uint32_t thresh, hipStream_t stream, bool rows32) {
-  static std::atomic<unsigned long long> done0{0}, done1{0};   // one bit per device (common.h)
-  int r = kbner_set_max_lds_once(done0, reinterpret_cast<const void*>(attn_fwd_kernel<NKB, DROP, false>), AT_LDS_BYTES);
+// The one launcher: raise the kernel's dynamic-LDS limit once per device, launch `grid` workgroups of AT_NW waves, map the error.
+template <auto KERNEL, typename... Args>
+static int launch_attn(dim3 grid, hipStream_t stream, Args... args) {
+  static std::atomic<unsigned long long> attr_done{0};   // per kernel, one bit per device (common.h)
+  const int r = kbner_set_max_lds_once(attr_done, reinterpret_cast<const void*>(KERNEL), AT_LDS_BYTES);
   if (r) return r;
-  r = kbner_set_max_lds_once(done1, reinterpret_cast<const void*>(attn_fwd_kernel<NKB, DROP, true>), AT_LDS_BYTES);
-  if (r) return r;
-  const int S = NKB * 16;
-  const int ncu = kbner_cu_count();
-  // 32 rows per wave and pass (round 3): half the LDS bytes per flop.  Not with dropout: in halves the keep tests push the S = 512
-  // instantiation over 256 VGPRs (94-148 spills), in quarters it fits but runs at 322 us against the 16-row kernel's 315
-  if (rows32 && !DROP && NKB % 4 == 0 && rpw % 256 == 0) {
-    constexpr int NP = (NKB % 8 == 0) ? KBNER_ATTN_PARTS : 2;
-    static std::atomic<unsigned long long> done2{0}, done3{0};
-    r = kbner_set_max_lds_once(done2, reinterpret_cast<const void*>(attn_fwd32_kernel<NKB, DROP, false, NP>), AT_LDS_BYTES);
-    if (r) return r;
-    r = kbner_set_max_lds_once(done3, reinterpret_cast<const void*>(attn_fwd32_kernel<NKB, DROP, true, NP>), AT_LDS_BYTES);
-    if (r) return r;
-    if (rpw == S && B * A >= 2 * ncu)
-      hipLaunchKernelGGL((attn_fwd32_kernel<NKB, DROP, true, NP>), dim3(ncu), dim3(512), AT_LDS_BYTES, stream, qkv, maskbias, ctx, ctx_lo,
-                         lse, H, A, 0.125f, rpw, seed, thresh, B * A);
-    else
-      hipLaunchKernelGGL((attn_fwd32_kernel<NKB, DROP, false, NP>), dim3((S + rpw - 1) / rpw, A, B), dim3(512), AT_LDS_BYTES, stream,
-                         qkv, maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw, seed, thresh, 1);
-    hipError_t e32 = hipGetLastError();
-    return e32 == hipSuccess ? 0 : -(int)e32;
-  }
-  if (rpw == S && B * A >= 2 * ncu) {   // whole heads, at least two per CU: walk them persistently, prefetching the next (-4 % at
-                                        // full length, -8 % with ragged masks, tools/attn_bench.py at B = 128)
-    hipLaunchKernelGGL((attn_fwd_kernel<NKB, DROP, true>), dim3(ncu), dim3(512), AT_LDS_BYTES, stream, qkv, maskbias, ctx, ctx_lo, lse, H,
-                       A, 0.125f, rpw, seed, thresh, B * A);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<NKB, DROP, false>), dim3((S + rpw - 1) / rpw, A, B), dim3(512), AT_LDS_BYTES, stream, qkv,
-                       maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw, seed, thresh, 1);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
+  hipLaunchKernelGGL(KERNEL, grid, dim3(AT_NW * 64), AT_LDS_BYTES, stream, args...);
+  KBNER_LAUNCH_RET();
 }
-template <int NKB>
+
+// Only kernels that a shape can reach are instantiated.  pick_rpw returns rpw == S (whole heads: the persistent walk) only for
+// S in {128, 256, 512} and a multiple of 256 only for S >= 192 (tests/test_mmaref_cpu.py pins both); the 32-row kernel is not used
+// with dropout: in halves the keep tests push the S = 512 instantiation over 256 VGPRs (94-148 spills), in quarters it fits but
+// runs at 322 us against the 16-row kernel's 315.  Whatever these exclude runs on the 16-row / non-persistent kernel.
+template <int NKB, bool DROP>
 static int launch_attn_fwd(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, uint8_t* ctx_lo, float* lse, int B, int H, int A, int rpw,
                            uint32_t seed, uint32_t thresh, hipStream_t stream, bool rows32) {
-  if (thresh) return launch_attn_fwd2<NKB, true>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, seed, thresh, stream, rows32);
-  return launch_attn_fwd2<NKB, false>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, seed, thresh, stream, rows32);
+  constexpr int S = NKB * 16;
+  constexpr bool CAN_PERSIST = NKB == 8 || NKB == 16 || NKB == 32;
+  constexpr bool CAN_ROWS32 = !DROP && NKB % 4 == 0 && NKB >= 12;
+  const int ncu = kbner_cu_count();
+  // whole heads, at least two per CU: walk them persistently, prefetching the next (-4 % at full length, -8 % with ragged masks,
+  // tools/attn_bench.py at B = 128)
+  const bool persist = rpw == S && B * A >= 2 * ncu;
+  const dim3 tiles((S + rpw - 1) / rpw, A, B);
+  // 32 rows per wave and pass (round 3): half the LDS bytes per flop
+  if constexpr (CAN_ROWS32) {
+    if (rows32 && rpw % 256 == 0) {
+      constexpr int NP = (NKB % 8 == 0) ? KBNER_ATTN_PARTS : 2;
+      if constexpr (CAN_PERSIST) {
+        if (persist)
+          return launch_attn<attn_fwd32_kernel<NKB, DROP, true, NP>>(dim3(ncu), stream, qkv, maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw,
+                                                                     seed, thresh, B * A);
+      }
+      return launch_attn<attn_fwd32_kernel<NKB, DROP, false, NP>>(tiles, stream, qkv, maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw, seed,
+                                                                  thresh, 1);
+    }
+  }
+  if constexpr (CAN_PERSIST) {
+    if (persist)
+      return launch_attn<attn_fwd_kernel<NKB, DROP, true>>(dim3(ncu), stream, qkv, maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw, seed,
+                                                           thresh, B * A);
+  }
+  return launch_attn<attn_fwd_kernel<NKB, DROP, false>>(tiles, stream, qkv, maskbias, ctx, ctx_lo, lse, H, A, 0.125f, rpw, seed, thresh, 1);
 }
 
 #ifdef KBNER_ATTN_LAB
 // Lab builds only (-DKBNER_ATTN_LAB, linked with tools/experiments/attention3.hip): the round-3 streaming forward and the A/B
-// switch KBNER_ATTN (1 = the 16-row-per-pass forward, 3 = streaming forward where it applies, 4 = forced).  The product
-// library has neither: it reads no environment variable.
+// switch KBNER_ATTN (1 = the 16-row-per-pass forward, 3 = streaming forward where it applies, 4 = forced, 5 = the pipelined
+// backward stream).  The product library has neither: it reads no environment variable.
 int kbner_attn_fwd3(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, float* lse, int B, int S, int H, int A,
                     uint32_t drop_seed, uint32_t drop_thresh, hipStream_t stream);
 static int attn_variant() {
@@ -1241,60 +1138,29 @@ static int attn_variant() {
 #endif
 
 template <bool DROP, bool RES>
-static int launch_attn_bwd2(const bf16_t* qkv, const bf16_t* ctx, const uint8_t* ctx_lo, const bf16_t* dctx, const float* maskbias,
-                            const float* lse, float* Dws, bf16_t* dqkv, int B, int S, int H, int A, uint32_t seed, uint32_t thresh,
-                            float* dbias, hipStream_t s) {
-  static std::atomic<unsigned long long> done0{0}, done1{0}, done2{0}, done3{0};   // one bit per device (common.h)
-  int r = kbner_set_max_lds_once(done0, reinterpret_cast<const void*>(attn_bwd_dq_kernel<DROP, RES>), AT_LDS_BYTES);
-  if (r) return r;
-  r = kbner_set_max_lds_once(done1, reinterpret_cast<const void*>(attn_bwd_dkv_kernel<DROP>), AT_LDS_BYTES);
-  if (r) return r;
-  int rpw = pick_rpw(B, S, A);
-  if (rpw < 16 * AT_NWB) rpw = 16 * AT_NWB;  // every wave owns at least one 16-row pass
-  const dim3 grid((S + rpw - 1) / rpw, A, B);
-  // 32-row-stationary kernels whenever a workgroup's row tile gives each of its 8 waves whole 32-row passes
-  if (rpw % 256 == 0 && S % 32 == 0) {
-    r = kbner_set_max_lds_once(done2, reinterpret_cast<const void*>(attn_bwd_dq2_kernel<DROP, RES>), AT_LDS_BYTES);
-    if (r) return r;
-    r = kbner_set_max_lds_once(done3, reinterpret_cast<const void*>(attn_bwd_dkv2_kernel<DROP>), AT_LDS_BYTES);
-    if (r) return r;
-#ifdef KBNER_ATTN_LAB
-    if (!DROP && attn_variant() == 5) {   // KBNER_ATTN=5: the pipelined backward stream (lab builds)
-      static std::atomic<unsigned long long> done4{0}, done5{0};
-      r = kbner_set_max_lds_once(done4, reinterpret_cast<const void*>(attn_bwd_dq3_kernel<RES>), AT_LDS_BYTES);
-      if (r) return r;
-      r = kbner_set_max_lds_once(done5, reinterpret_cast<const void*>(attn_bwd_dkv3_kernel), AT_LDS_BYTES);
-      if (r) return r;
-      hipLaunchKernelGGL((attn_bwd_dq3_kernel<RES>), grid, dim3(512), AT_LDS_BYTES, s, qkv, dctx, ctx, ctx_lo, maskbias, lse, Dws, dqkv, S,
-                         H, A, 0.125f, rpw, dbias);
-      hipLaunchKernelGGL(attn_bwd_dkv3_kernel, grid, dim3(512), AT_LDS_BYTES, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw,
-                         dbias);
-      hipError_t e3 = hipGetLastError();
-      return e3 == hipSuccess ? 0 : -(int)e3;
-    }
-#endif
-    hipLaunchKernelGGL((attn_bwd_dq2_kernel<DROP, RES>), grid, dim3(512), AT_LDS_BYTES, s, qkv, dctx, ctx, ctx_lo, maskbias, lse, Dws,
-                       dqkv, S, H, A, 0.125f, rpw, seed, thresh, dbias);
-    hipLaunchKernelGGL(attn_bwd_dkv2_kernel<DROP>, grid, dim3(512), AT_LDS_BYTES, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A,
-                       0.125f, rpw, seed, thresh, dbias);
-    hipError_t e2 = hipGetLastError();
-    return e2 == hipSuccess ? 0 : -(int)e2;
-  }
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<DROP, RES>), grid, dim3(AT_NWB * 64), AT_LDS_BYTES, s, qkv, dctx, ctx, ctx_lo, maskbias, lse,
-                     Dws, dqkv, S, H, A, 0.125f, rpw, seed, thresh, dbias);
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<DROP>, grid, dim3(AT_NWB * 64), AT_LDS_BYTES, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A,
-                     0.125f, rpw, seed, thresh, dbias);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : -(int)e;
-}
-template <bool DROP>
 static int launch_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const uint8_t* ctx_lo, const bf16_t* dctx, const float* maskbias,
                            const float* lse, float* Dws, bf16_t* dqkv, int B, int S, int H, int A, uint32_t seed, uint32_t thresh,
                            float* dbias, hipStream_t s) {
-  if (ctx_lo) return launch_attn_bwd2<DROP, true>(qkv, ctx, ctx_lo, dctx, maskbias, lse, Dws, dqkv, B, S, H, A, seed, thresh, dbias, s);
-  return launch_attn_bwd2<DROP, false>(qkv, ctx, ctx_lo, dctx, maskbias, lse, Dws, dqkv, B, S, H, A, seed, thresh, dbias, s);
+  const int rpw = pick_rpw(B, S, A);   // >= 128: every wave owns at least one 16-row pass
+  const dim3 grid((S + rpw - 1) / rpw, A, B);
+  int r;
+  // 32-row-stationary kernels whenever a workgroup's row tile gives each of its 8 waves whole 32-row passes
+  if (rpw % 256 == 0 && S % 32 == 0) {
+#ifdef KBNER_ATTN_LAB
+    if (!DROP && attn_variant() == 5) {   // the pipelined backward stream (tools/experiments/attn_bwd3.h)
+      r = launch_attn<attn_bwd_dq3_kernel<RES>>(grid, s, qkv, dctx, ctx, ctx_lo, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, dbias);
+      return r ? r : launch_attn<attn_bwd_dkv3_kernel>(grid, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, dbias);
+    }
+#endif
+    r = launch_attn<attn_bwd_dq2_kernel<DROP, RES>>(grid, s, qkv, dctx, ctx, ctx_lo, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, seed,
+                                                    thresh, dbias);
+    return r ? r : launch_attn<attn_bwd_dkv2_kernel<DROP>>(grid, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, seed, thresh,
+                                                           dbias);
+  }
+  r = launch_attn<attn_bwd_dq_kernel<DROP, RES>>(grid, s, qkv, dctx, ctx, ctx_lo, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, seed,
+                                                 thresh, dbias);
+  return r ? r : launch_attn<attn_bwd_dkv_kernel<DROP>>(grid, s, qkv, dctx, maskbias, lse, Dws, dqkv, S, H, A, 0.125f, rpw, seed, thresh, dbias);
 }
-
 
 extern "C" {
 
@@ -1315,16 +1181,20 @@ int kbner_attn_fwd(const bf16_t* qkv, const float* maskbias, bf16_t* ctx, uint8_
 #else
   const bool rows32 = true;   // 32 query rows per wave and pass wherever launch_attn_fwd can use them (no dropout, >= 256 rows)
 #endif
+#define FWD(NKB)                                                                                                       \
+  (drop_thresh ? launch_attn_fwd<NKB, true>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32) \
+               : launch_attn_fwd<NKB, false>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32))
   switch (S / 64) {
-    case 1: return launch_attn_fwd<4>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 2: return launch_attn_fwd<8>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 3: return launch_attn_fwd<12>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 4: return launch_attn_fwd<16>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 5: return launch_attn_fwd<20>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 6: return launch_attn_fwd<24>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    case 7: return launch_attn_fwd<28>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
-    default: return launch_attn_fwd<32>(qkv, maskbias, ctx, ctx_lo, lse, B, H, A, rpw, drop_seed, drop_thresh, st, rows32);
+    case 1: return FWD(4);
+    case 2: return FWD(8);
+    case 3: return FWD(12);
+    case 4: return FWD(16);
+    case 5: return FWD(20);
+    case 6: return FWD(24);
+    case 7: return FWD(28);
+    default: return FWD(32);
   }
+#undef FWD
 }
 
 // dctx bf16 [B*S,H] (dO) ; ctx (O) ; lse ; Dws f32 [B,A,S] workspace ; dqkv bf16 [B*S,3H] out ;
@@ -1342,8 +1212,10 @@ int kbner_attn_bwd(const bf16_t* qkv, const bf16_t* ctx, const uint8_t* ctx_lo, 
                    float* dbias_qkv, void* stream) {
   KBNER_CHECK_ARG(B > 0 && A > 0 && H == A * AT_D && S % 64 == 0 && S >= 64 && S <= AT_MAXS);
   hipStream_t s = (hipStream_t)stream;
-  if (drop_thresh) return launch_attn_bwd<true>(qkv, ctx, ctx_lo, dctx, maskbias, lse, Dws, dqkv, B, S, H, A, drop_seed, drop_thresh, dbias_qkv, s);
-  return launch_attn_bwd<false>(qkv, ctx, ctx_lo, dctx, maskbias, lse, Dws, dqkv, B, S, H, A, drop_seed, drop_thresh, dbias_qkv, s);
+#define BWD(DROP, RES) launch_attn_bwd<DROP, RES>(qkv, ctx, ctx_lo, dctx, maskbias, lse, Dws, dqkv, B, S, H, A, drop_seed, drop_thresh, dbias_qkv, s)
+  if (drop_thresh) return ctx_lo ? BWD(true, true) : BWD(true, false);
+  return ctx_lo ? BWD(false, true) : BWD(false, false);
+#undef BWD
 }
 
 }  // extern "C"

@@ -6,9 +6,15 @@
 #define AT_D 64
 #define AT_MAXS 512
 #define AT_NW 8  // wavefronts per workgroup (2 per SIMD: one wave's softmax VALU overlaps the other's MFMAs)
-#ifndef AT_NWB
-#define AT_NWB 8  // wavefronts per workgroup of the two backward kernels (-DAT_NWB=16, 4 waves per SIMD at 128 VGPRs, measured no faster)
-#endif
+
+// Dynamic LDS of every attention kernel: two [AT_MAXS][64] bf16 panels (K, V or Q, dO) in 128-byte rows, then three AT_MAXS-long
+// rows of 4-byte values (forward, dQ: mask, dropout column keys ; dK/dV: lse, D, dropout row keys).
+#define AT_LDS_BYTES (2 * AT_MAXS * 128 + 3 * AT_MAXS * 4)
+static __device__ __forceinline__ unsigned char* at_panel(unsigned char* smem, int i) { return smem + i * AT_MAXS * 128; }
+template <typename T>
+static __device__ __forceinline__ T* at_row(unsigned char* smem, int i) {
+  return reinterpret_cast<T*>(smem + 2 * AT_MAXS * 128 + i * AT_MAXS * 4);
+}
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_cvoid;
@@ -50,29 +56,6 @@ static __device__ __forceinline__ void stage_panel(const bf16_t* __restrict__ sr
     const int pos = lane & 7;
     glds16(src + (size_t)row * ld + ((pos ^ kc_swz(row)) << 3), s + q * 1024);
   }
-}
-
-// 16 rows (r0 + lane&15) x 32 k (ks): k-contiguous fragment, ds_read_b128
-static __device__ __forceinline__ bf16x8 kc_frag(const unsigned char* s, int r0, int ks, int lane) {
-  const int row = r0 + (lane & 15);
-  const int c = ks * 4 + (lane >> 4);
-  const s8v v = *reinterpret_cast<const s8v*>(s + row * 128 + ((c ^ kc_swz(row)) << 4));
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// transposed fragment: 16 "rows" = panel columns db*16 + (lane&15); k = panel rows of the 32-row
-// chunk kc in the split order {g*4+j (j<4), 16+g*4+(j-4)} that matches two stacked 16x16 C tiles
-static __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* s, int kc, int db, int lane) {
-  const int p = lane & 15;
-  const int row = kc * 32 + (lane >> 4) * 4 + (p >> 2);
-  const int c = db * 2 + ((p & 3) >> 1);
-  const unsigned char* a = s + row * 128 + ((c ^ kc_swz(row)) << 4) + ((p & 1) << 3);
-  const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a));
-  const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(a + 16 * 128));
-  s8v v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
 }
 
 // stationary fragment straight from global: row (r0 + lane&15), 8 consecutive d at ks*32 + g*8
@@ -173,6 +156,8 @@ static __device__ __forceinline__ PanelBases panel_bases(const unsigned char* s,
 static __device__ __forceinline__ bf16x8 kc_at(const unsigned char* base, int off) {
   return __builtin_bit_cast(bf16x8, *reinterpret_cast<const s8v*>(base + off));
 }
+// transposed fragment: 16 "rows" = panel columns db*16 + (lane&15); k = panel rows of a 32-row chunk in the split order
+// {g*4+j (j<4), 16+g*4+(j-4)} that matches two stacked 16x16 C tiles
 static __device__ __forceinline__ bf16x8 tr_at(const unsigned char* base, int off) {
   const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(base + off));
   const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s4v __attribute__((address_space(3)))*)(base + off + 16 * 128));
@@ -182,3 +167,66 @@ static __device__ __forceinline__ bf16x8 tr_at(const unsigned char* base, int of
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// T = a . b^T over the whole head dimension (two k-steps of 32) on top of C.  Macros, like the epilogues below: as functions
+// they compute the same but hipcc orders the kernels' instructions differently.
+#define AT_MFMA2(T, A0, A1, B0, B1, C) \
+  T = MFMA((A0), (B0), (C));           \
+  T = MFMA((A1), (B1), T)
+// T0 | T1 = the two 16-row tiles of the 32-row chunk at byte offset CO of panel P (PanelBases) against the stationary fragments
+// X0 | X1, on top of I0 | I1: the score tiles (K or Q panel) and the dP tiles (V or dO panel) of the 16-row backward kernels
+#define AT_CHUNK_MFMA(T0, T1, P, CO, X0, X1, I0, I1)                                \
+  AT_MFMA2(T0, kc_at((P).kc[0], (CO)), kc_at((P).kc[1], (CO)), X0, X1, I0);         \
+  AT_MFMA2(T1, kc_at((P).kc[0], (CO) + 2048), kc_at((P).kc[1], (CO) + 2048), X0, X1, I1)
+
+// four consecutive dropout keys (column keys of a 16-key fragment, row keys of a 16-query one: entries g*4 .. g*4 + 3)
+static __device__ __forceinline__ void load_keys4(const uint32_t* p, uint32_t (&k)[4]) {
+  const uint4 c = *reinterpret_cast<const uint4*>(p);
+  k[0] = c.x; k[1] = c.y; k[2] = c.z; k[3] = c.w;
+}
+// forward: the probabilities a of query key rk against the four column keys at ck, dropped ones zeroed
+static __device__ __forceinline__ f4v drop_zero4(f4v a, uint32_t rk, const uint32_t* ckp, uint32_t thresh) {
+  const uint4 ck = *reinterpret_cast<const uint4*>(ckp);
+  a[0] = drop_keep(rk, ck.x, thresh) ? a[0] : 0.0f;
+  a[1] = drop_keep(rk, ck.y, thresh) ? a[1] : 0.0f;
+  a[2] = drop_keep(rk, ck.z, thresh) ? a[2] : 0.0f;
+  a[3] = drop_keep(rk, ck.w, thresh) ? a[3] : 0.0f;
+  return a;
+}
+
+// D = rowdot(dO, O) of this lane's row from the two fragments of each; RES adds the residual O - bf16(O) the forward kept
+template <bool RES>
+static __device__ __forceinline__ float rowdot_do_o(bf16x8 do0, bf16x8 do1, bf16x8 of0, bf16x8 of1, const uint32_t (&rw)[4]) {
+  // each lane group g holds 16 of the row's 64 d in its two fragments
+  float d_part = dot8(do0, of0) + dot8(do1, of1);
+  if (RES) d_part += res_dot16(do0, do1, rw);   // D to ~12 bits of O (see kbner_attn_bwd)
+  return group4_sum(d_part);
+}
+
+// backward epilogue, d-block DB of a 16-row block: ACC[DB] * SC as bf16 to ROW (this lane's row: columns DB*16 + g*4 .. +3)
+#define AT_STORE_SCALED(ACC, SC, ROW, DB)                             \
+  {                                                                   \
+    uint2 u;                                                          \
+    u.x = pack2bf((ACC)[DB][0] * (SC), (ACC)[DB][1] * (SC));          \
+    u.y = pack2bf((ACC)[DB][2] * (SC), (ACC)[DB][3] * (SC));          \
+    *reinterpret_cast<uint2*>((ROW) + (DB) * 16 + g * 4) = u;         \
+  }
+
+// forward epilogue of the 16-row block at query Q0: O = ACC * INV as bf16 to ctx (O^T fragment: lane holds O[Q0+li][db*16 + g*4
+// .. +3]), its rounding residual O - bf16(O) to ctx_lo (nullable; one byte per element, 16 B per lane: at_res_block, see
+// kbner_attn_bwd), lse = ln 2 * (M2 + log2 SUM) with M2 the row maximum in the log2 domain and SUM the softmax normaliser.
+// (Q0 is a sum that joins the index sums unparenthesised: the association is part of the instruction stream.)
+#define AT_STORE_CTX(ACC, INV, M2, SUM, Q0)                                                                                  \
+  {                                                                                                                          \
+    const float inv = (INV);                                                                                                 \
+    bf16_t* orow = ctx + (size_t)(b * S + Q0 + li) * H + h * AT_D;                                                           \
+    uint32_t res[4];                                                                                                         \
+    _Pragma("unroll") for (int db = 0; db < 4; ++db) {                                                                       \
+      uint2 u;                                                                                                               \
+      u.x = pack2bf_res8((ACC)[db][0] * inv, (ACC)[db][1] * inv, res[db], false);                                            \
+      u.y = pack2bf_res8((ACC)[db][2] * inv, (ACC)[db][3] * inv, res[db], true);                                             \
+      *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;                                                                 \
+    }                                                                                                                        \
+    if (ctx_lo)                                                                                                              \
+      *reinterpret_cast<uint4*>(at_res_block(ctx_lo, b, A, h, S, (Q0)) + lane * 16) = make_uint4(res[0], res[1], res[2], res[3]); \
+    if (g == 0) lse[((size_t)b * A + h) * S + Q0 + li] = ((M2) + __log2f(SUM)) * 0.6931471805599453f;                          \
+  }

@@ -249,6 +249,17 @@ def test_pick_rpw_routes_named_in_the_case_list():
     assert {c[1] for c in mmaref.ONEHOT_CASES} == set(range(64, 513, 64))
 
 
+def test_pick_rpw_never_reaches_the_forward_kernels_that_are_not_instantiated():
+    """csrc/attention.hip launch_attn_fwd instantiates the 32-row forward (needs rpw % 256 == 0) only for S >= 192 and the
+    persistent walk (rpw == S) only for S in {128, 256, 512}: pick_rpw offers nothing else."""
+    batches = list(range(1, 600)) + [1024, 4096, 65536]
+    for S in range(64, 513, 64):
+        rpws = {mmaref.pick_rpw(B, S, A) for A in (1, 2, 3, 4, 8, 12, 16, 24, 32, 64) for B in batches}
+        assert rpws <= {128, 256, 512}
+        assert S >= 192 or not any(r % 256 == 0 for r in rpws), (S, rpws)
+        assert S in (128, 256, 512) or S not in rpws, (S, rpws)
+
+
 def test_e5m2_round_and_the_dropout_residual_mechanism():
     """the residual byte's rounding, and what it does in the one-hot case with dropout: the fused forward exponent leaves
     e = 1 + delta, the dropout path divides by the float32 sum of e, the residual hands O = 2 V / (1 + delta) to D -> the

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd3_kernel(const bf16_t* __restr
       a3_dma_block(qkv + (size_t)b * S * ld + h * AT_D + 2 * H, ld, blk, sV, blk, wid, lane);
     }
   }
-  // per-lane fragment address parts (see kc_frag / tr_frag): K rows f*16 + li -> + f*2048 ; V rows kc*32 + g*4 + (li>>2) -> + kc*4096
+  // per-lane fragment address parts (the offsets panel_bases() adds to a panel): K rows f*16 + li -> + f*2048 ; V rows kc*32 + g*4 + (li>>2) -> + kc*4096
   const unsigned kl0 = li * 128 + (((0 * 4 + g) ^ kc_swz(li)) << 4);
   const int vrow = g * 4 + (li >> 2);
   const unsigned vl0 = vrow * 128 + (((0 * 2 + ((li & 3) >> 1)) ^ kc_swz(vrow)) << 4) + ((li & 1) << 3);

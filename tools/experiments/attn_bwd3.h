@@ -61,11 +61,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq3_kernel(const bf16_t* __restr
                                                           bf16_t* __restrict__ dqkv, int S, int H, int A, float scale, int rpw,
                                                           float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8][64];
+  __shared__ float red[AT_NW][64];
   __shared__ int sKlen[2];
-  unsigned char* sK = smem;
-  unsigned char* sV = smem + AT_MAXS * 128;
-  float* sMask = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
+  unsigned char *sK = at_panel(smem, 0), *sV = at_panel(smem, 1);
+  float* sMask = at_row<float>(smem, 0);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -74,8 +73,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq3_kernel(const bf16_t* __restr
   f4v bsum[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsum[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  stage_panel<8>(base + H, ld, S, sK, wid, lane);
-  stage_panel<8>(base + 2 * H, ld, S, sV, wid, lane);
+  stage_panel(base + H, ld, S, sK, wid, lane);
+  stage_panel(base + 2 * H, ld, S, sV, wid, lane);
   int nfree;
   const int klen = stage_mask_klen<512>(maskbias, (size_t)b * S, S, 1.0f / scale, sMask, sKlen, tid, nfree);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -115,9 +114,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq3_kernel(const bf16_t* __restr
       const int qj = q0 + j * 16;
       const size_t sidx = ((size_t)b * A + h) * S + qj + li;
       l_q[j] = -lse_q[j] / scale;   // accumulator start of the score MFMAs (attn_bwd_dq2_kernel)
-      float d_part = dot8(dof[j][0], of[j][0]) + dot8(dof[j][1], of[j][1]);
-      if (RES) d_part += res_dot16(dof[j][0], dof[j][1], rw[j]);
-      d_q[j] = group4_sum(d_part);
+      d_q[j] = rowdot_do_o<RES>(dof[j][0], dof[j][1], of[j][0], of[j][1], rw[j]);
       if (g == 0) Dv[sidx] = d_q[j];
 #pragma unroll
       for (int db = 0; db < 4; ++db) dq[j][db] = zero4;
@@ -225,15 +222,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq3_kernel(const bf16_t* __restr
       bf16_t* orow = dqkv + (size_t)(b * S + q0 + j * 16 + li) * ld + h * AT_D;
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        uint2 u;
-        u.x = pack2bf(dq[j][db][0] * oscale, dq[j][db][1] * oscale);
-        u.y = pack2bf(dq[j][db][2] * oscale, dq[j][db][3] * oscale);
-        *reinterpret_cast<uint2*>(orow + db * 16 + g * 4) = u;
+        AT_STORE_SCALED(dq[j], oscale, orow, db)
         bsum[db] += dq[j][db] * oscale;
       }
     }
   }
-  if (dbias != nullptr) flush_colsum<8>(bsum, red, dbias + h * AT_D, wid, lane, tid);
+  if (dbias != nullptr) flush_colsum<AT_NW>(bsum, red, dbias + h * AT_D, wid, lane, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -244,22 +238,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv3_kernel(const bf16_t* __rest
                                                            const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, int S,
                                                            int H, int A, float scale, int rpw, float* __restrict__ dbias) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8][64];
+  __shared__ float red[AT_NW][64];
   f4v bsk[4], bsv[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) bsk[db] = bsv[db] = (f4v){0.f, 0.f, 0.f, 0.f};
-  unsigned char* sQ = smem;
-  unsigned char* sO = smem + AT_MAXS * 128;
-  float* sL = reinterpret_cast<float*>(smem + 2 * AT_MAXS * 128);
-  float* sD = sL + AT_MAXS;
+  unsigned char *sQ = at_panel(smem, 0), *sO = at_panel(smem, 1);
+  float *sL = at_row<float>(smem, 0), *sD = at_row<float>(smem, 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int ld = 3 * H;
   const bf16_t* base = qkv + (size_t)b * S * ld + h * AT_D;
   const bf16_t* dob = dctx + (size_t)b * S * H + h * AT_D;
-  stage_panel<8>(base, ld, S, sQ, wid, lane);
-  stage_panel<8>(dob, H, S, sO, wid, lane);
+  stage_panel(base, ld, S, sQ, wid, lane);
+  stage_panel(dob, H, S, sO, wid, lane);
   const size_t sbase = ((size_t)b * A + h) * S;
   for (int i = tid; i < AT_MAXS + 32; i += 512) {   // (+ one chunk: the last step's scores read one chunk past the end)
     const bool in = i < S;
@@ -434,23 +426,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv3_kernel(const bf16_t* __rest
       bf16_t* vrow = krow + H;
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        uint2 u;
         const float ks = scale;
-        u.x = pack2bf(dk[j][db][0] * ks, dk[j][db][1] * ks);
-        u.y = pack2bf(dk[j][db][2] * ks, dk[j][db][3] * ks);
-        *reinterpret_cast<uint2*>(krow + db * 16 + g * 4) = u;
-        uint2 w;
-        w.x = pack2bf(dv[j][db][0], dv[j][db][1]);
-        w.y = pack2bf(dv[j][db][2], dv[j][db][3]);
-        *reinterpret_cast<uint2*>(vrow + db * 16 + g * 4) = w;
+        AT_STORE_SCALED(dk[j], ks, krow, db)
+        AT_STORE_SCALED(dv[j], 1.0f, vrow, db)
         bsk[db] += dk[j][db] * ks;
         bsv[db] += dv[j][db];
       }
     }
   }
   if (dbias != nullptr) {
-    flush_colsum<8>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
-    flush_colsum<8>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsk, red, dbias + H + h * AT_D, wid, lane, tid);
+    flush_colsum<AT_NW>(bsv, red, dbias + 2 * H + h * AT_D, wid, lane, tid);
   }
 }
 #undef A3_UA
