@@ -53,9 +53,7 @@ static inline int kbner_cu_count() {
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 static __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // fp32 -> bf16 through the native conversion: hipcc lowers a pair to ONE v_cvt_pk_bf16_f32 (round-to-nearest-even)
@@ -66,6 +64,23 @@ static __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 static __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack2bf(f, 0.0f) & 0xffffu); }
+// packed bf16 pair (one dword) <-> f2v
+typedef float f2v __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ f2v unpack2bf(uint32_t w) {
+  return (f2v){__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+}
+// eight consecutive bf16 (one 16-byte access) <-> eight floats
+static __device__ __forceinline__ void unpack8bf(const uint4 u, float (&f)[8]) {
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = __uint_as_float(w[j] << 16);
+    f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+  }
+}
+static __device__ __forceinline__ uint4 pack8bf(const float* f) {
+  return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
+}
 
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -132,36 +147,20 @@ static __device__ __forceinline__ uint4 splitk_fold8_pack(const float* __restric
     for (int r = 0; r < 8; ++r) v[r] = drop_keep(rk, drop_colkey(drop_seed, (uint32_t)(n + r)), drop_thresh) ? v[r] * ds : 0.0f;
   }
   if (addend) {
-    const uint4 u = *reinterpret_cast<const uint4*>(addend + (size_t)m * ldadd + n);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    float a[8];
+    unpack8bf(*reinterpret_cast<const uint4*>(addend + (size_t)m * ldadd + n), a);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[2 * r] += __uint_as_float(w[r] << 16);
-      v[2 * r + 1] += __uint_as_float(w[r] & 0xffff0000u);
-    }
+    for (int r = 0; r < 8; ++r) v[r] += a[r];
   }
-  uint4 o;
-  o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]); o.z = pack2bf(v[4], v[5]); o.w = pack2bf(v[6], v[7]);
-  return o;
+  return pack8bf(v);
 }
 
-// GELU, erf form (HF hidden_act="gelu"), and its derivative.  erf by Abramowitz-Stegun 7.1.26
-// (|error| <= 1.5e-7, far below the bf16 rounding of the stored result) so the GEMM epilogue costs
-// one v_rcp + one v_exp + a 5-term Horner per element instead of libm erff; exp(-x^2/2) is shared
-// between the cdf and the pdf term of the derivative.
-static __device__ __forceinline__ void gelu_parts(float x, float& cdf, float& e) {
-  const float u = fabsf(x) * 0.70710678118654752f;
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * u);
-  e = __expf(-u * u);  // = exp(-x^2 / 2)
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erf_abs = 1.0f - poly * e;
-  cdf = 0.5f * (1.0f + copysignf(erf_abs, x));
-}
-// Two elements at a time on the packed fp32 pipe (v_pk_fma_f32 / v_pk_mul_f32: 2 lanes-worth per issue): the GEMM
-// epilogues that apply GELU / GELU' are VALU-bound (128 elements per lane per 256x256 tile), so halving the issue
-// count of the polynomial part is worth ~10 % of those GEMMs.  Same A&S 7.1.26 arithmetic as gelu_parts, refactored so
-// that no copysign is needed for the forward:  x*cdf = 0.5 x + |x| (0.5 - 0.5 p e).
-typedef float f2v __attribute__((ext_vector_type(2)));
+// GELU, erf form (HF hidden_act="gelu"), and its derivative, two elements at a time on the packed fp32 pipe (v_pk_fma_f32 /
+// v_pk_mul_f32: 2 lanes-worth per issue): the GEMM epilogues that apply GELU / GELU' are VALU-bound (128 elements per lane per
+// 256x256 tile), so halving the issue count of the polynomial part is worth ~10 % of those GEMMs.  erf by Abramowitz-Stegun 7.1.26
+// (|error| <= 1.5e-7, far below the bf16 rounding of the stored result): one v_rcp + one v_exp + a 5-term Horner per element
+// instead of libm erff; exp(-x^2/2) is shared between the cdf and the pdf term of the derivative, and the forward needs no
+// copysign:  x*cdf = 0.5 x + |x| (0.5 - 0.5 p e).  (The rejected one-logistic form: tools/experiments/gelu_logistic.h.)
 static __device__ __forceinline__ f2v splat2(float a) { return (f2v){a, a}; }
 // h = 0.5 - 0.5 * poly(t) * e  (= 0.5 * erf(|x| / sqrt 2)),  e = exp(-x^2 / 2)
 static __device__ __forceinline__ void gelu_half_erf2(f2v x, f2v ax, f2v& h, f2v& e) {
@@ -176,75 +175,21 @@ static __device__ __forceinline__ void gelu_half_erf2(f2v x, f2v ax, f2v& h, f2v
   p = p * t;
   h = splat2(0.5f) - p * e;
 }
-// Round 4 experiment, NOT the default (-DKBNER_GELU_LOGISTIC selects it): gelu / gelu' through ONE logistic per element instead of
-// the erf series:
-//     Phi(x) ~= s(x) = 1 / (1 + exp(-(x (p0 + p1 x^2 + p2 x^4))))        gelu = x s,   gelu' = s + x s (1 - s) (p0 + 3 p1 x^2 + 5 p2 x^4)
-// p fitted (minimax) to |gelu error| <= 3.8e-5 and |gelu' error| <= 9.3e-5 in fp32, 11 packed fp32 operations + 2 v_exp + 2 v_rcp per
-// element PAIR instead of 17 + 4.  Measured on one box, alternating processes: 945.1 / 945.1 sentences/s against 945.0 / 943.0 with
-// the erf series -- 4 of the ~30 vector instructions per element pair of an epilogue that is one of nine GEMMs: 0.3 %
-// of the step, inside the noise.  No measurable speed for a 250 times larger error: rejected.
-// x^2 is clamped at 36: beyond |x| = 6 the fit's polynomial is not monotone, s is 0 / 1 to 1e-9 there.
-#define KBNER_GELU_P0 1.59484492f
-#define KBNER_GELU_P1 7.40112029e-02f
-#define KBNER_GELU_P2 -6.97126291e-04f
-static __device__ __forceinline__ void gelu_logistic2(f2v x, f2v& sg, f2v& x2c) {
-  const f2v x2 = x * x;
-  x2c = (f2v){fminf(x2[0], 36.0f), fminf(x2[1], 36.0f)};
-  // -log2(e) folded into the coefficients: e = 2^(x * t) = exp(-u)
-  f2v t = x2c * splat2(-1.4426950408889634f * KBNER_GELU_P2) + splat2(-1.4426950408889634f * KBNER_GELU_P1);
-  t = t * x2c + splat2(-1.4426950408889634f * KBNER_GELU_P0);
-  const f2v a = x * t;
-  const f2v d = (f2v){__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])} + splat2(1.0f);
-  sg = (f2v){__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-}
-static __device__ __forceinline__ f2v gelu2_logistic(f2v x) {
-  f2v sg, x2c;
-  gelu_logistic2(x, sg, x2c);
-  return x * sg;
-}
-static __device__ __forceinline__ void gelu_both2_logistic(f2v x, f2v& y, f2v& dy) {
-  f2v sg, x2c;
-  gelu_logistic2(x, sg, x2c);
-  y = x * sg;
-  f2v du = x2c * splat2(5.0f * KBNER_GELU_P2) + splat2(3.0f * KBNER_GELU_P1);
-  du = du * x2c + splat2(KBNER_GELU_P0);
-  const f2v w = sg - sg * sg;
-  dy = (x * w) * du + sg;
-}
-// (the erf series of rounds 1-3, kept for tools / tests that want the 1.5e-7 form)
-static __device__ __forceinline__ f2v gelu2_erf(f2v x) {
+static __device__ __forceinline__ f2v gelu2(f2v x) {
   const f2v ax = {fabsf(x[0]), fabsf(x[1])};
   f2v h, e;
   gelu_half_erf2(x, ax, h, e);
   return x * splat2(0.5f) + ax * h;
 }
-static __device__ __forceinline__ f2v gelu_grad2(f2v x) {
-  const f2v ax = {fabsf(x[0]), fabsf(x[1])};
-  f2v h, e;
-  gelu_half_erf2(x, ax, h, e);
-  const f2v sh = {copysignf(h[0], x[0]), copysignf(h[1], x[1])};
-  return (x * e) * splat2(0.39894228040143268f) + (sh + splat2(0.5f));
-}
 // gelu(x) and gelu'(x) together (they share exp(-x^2/2) and the erf): the forward GEMM epilogue stores the derivative
 // (bf16) next to the activation, so the backward epilogue is one multiply instead of a second erf evaluation
-static __device__ __forceinline__ void gelu_both2_erf(f2v x, f2v& y, f2v& dy) {
+static __device__ __forceinline__ void gelu_both2(f2v x, f2v& y, f2v& dy) {
   const f2v ax = {fabsf(x[0]), fabsf(x[1])};
   f2v h, e;
   gelu_half_erf2(x, ax, h, e);
   y = x * splat2(0.5f) + ax * h;
   const f2v sh = {copysignf(h[0], x[0]), copysignf(h[1], x[1])};
   dy = (x * e) * splat2(0.39894228040143268f) + (sh + splat2(0.5f));
-}
-#ifdef KBNER_GELU_LOGISTIC
-static __device__ __forceinline__ f2v gelu2(f2v x) { return gelu2_logistic(x); }
-static __device__ __forceinline__ void gelu_both2(f2v x, f2v& y, f2v& dy) { gelu_both2_logistic(x, y, dy); }
-#else
-static __device__ __forceinline__ f2v gelu2(f2v x) { return gelu2_erf(x); }
-static __device__ __forceinline__ void gelu_both2(f2v x, f2v& y, f2v& dy) { gelu_both2_erf(x, y, dy); }
-#endif
-// packed bf16 pair (one dword) <-> f2v
-static __device__ __forceinline__ f2v unpack2bf(uint32_t w) {
-  return (f2v){__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
 }
 
 // bf16 pair; what the rounding dropped goes, scaled by 2^14, into one half (hi_half) of `res` as two e5m2 bytes
@@ -260,15 +205,4 @@ static __device__ __forceinline__ uint32_t pack2bf_res8(float lo, float hi, uint
   res = hi_half ? (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(rl, rh, (int)res, true)
                 : (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(rl, rh, 0, false);
   return w;
-}
-
-static __device__ __forceinline__ float gelu_f(float x) {
-  float cdf, e;
-  gelu_parts(x, cdf, e);
-  return x * cdf;
-}
-static __device__ __forceinline__ float gelu_grad_f(float x) {
-  float cdf, e;
-  gelu_parts(x, cdf, e);
-  return cdf + x * e * 0.39894228040143268f;
 }

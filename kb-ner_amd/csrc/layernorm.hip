@@ -8,75 +8,45 @@
 //   bwd : dh = rstd * (g - mean_H(g) - xhat * mean_H(g * xhat)),  g = dy * gamma
 //         dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy ; dbias += sum_rows dh (optional:
 //         the bias gradient of the GEMM whose output fed this LayerNorm's input)
-// H must be a multiple of 8 and <= 1024 (XLM-R base 768 / large 1024).
+// H must be a multiple of 8 and <= LN_MAXH = 1024 (XLM-R base 768 / large 1024).
 #include "common.h"
 
-#define LN_MAXCH 2  // 16-byte chunks per lane: H <= 64 * 8 * 2
+#define LN_MAXCH 2  // 16-byte chunks per lane
+#define LN_MAXH (64 * 8 * LN_MAXCH)
+
+// first column of a lane's c-th chunk of a row (a wave covers 64 x 8 consecutive columns per chunk)
+static __device__ __forceinline__ int ln_col(int lane, int c) { return (lane + 64 * c) * 8; }
 
 template <int NCH>
 struct RowF {
   float v[NCH][8];
 };
-
-template <int NCH>
-static __device__ __forceinline__ void load_row_bf16(const bf16_t* __restrict__ p, int H, int lane, RowF<NCH>& r) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int h0 = (lane + 64 * c) * 8;
-    if (h0 < H) {
-      const uint4 u = *reinterpret_cast<const uint4*>(p + h0);
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        r.v[c][2 * j] = __uint_as_float(w[j] << 16);
-        r.v[c][2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[c][j] = 0.0f;
-    }
-  }
-}
-
 // raw (unconverted) row image: lets the backward kernel fetch row r+stride while it reduces row r
 template <int NCH>
 struct RowRaw {
   uint4 v[NCH];
 };
+
 template <int NCH>
 static __device__ __forceinline__ void load_row_raw(const bf16_t* __restrict__ p, int H, int lane, RowRaw<NCH>& r) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const int h0 = (lane + 64 * c) * 8;
+    const int h0 = ln_col(lane, c);
     r.v[c] = (h0 < H) ? *reinterpret_cast<const uint4*>(p + h0) : make_uint4(0u, 0u, 0u, 0u);
   }
 }
 template <int NCH>
 static __device__ __forceinline__ void unpack_row(const RowRaw<NCH>& raw, RowF<NCH>& r) {
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const uint32_t w[4] = {raw.v[c].x, raw.v[c].y, raw.v[c].z, raw.v[c].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      r.v[c][2 * j] = __uint_as_float(w[j] << 16);
-      r.v[c][2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  }
+  for (int c = 0; c < NCH; ++c) unpack8bf(raw.v[c], r.v[c]);
 }
 
 template <int NCH>
 static __device__ __forceinline__ void store_row_bf16(bf16_t* __restrict__ p, int H, int lane, const RowF<NCH>& r) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const int h0 = (lane + 64 * c) * 8;
-    if (h0 < H) {
-      uint4 u;
-      u.x = pack2bf(r.v[c][0], r.v[c][1]);
-      u.y = pack2bf(r.v[c][2], r.v[c][3]);
-      u.z = pack2bf(r.v[c][4], r.v[c][5]);
-      u.w = pack2bf(r.v[c][6], r.v[c][7]);
-      *reinterpret_cast<uint4*>(p + h0) = u;
-    }
+    const int h0 = ln_col(lane, c);
+    if (h0 < H) *reinterpret_cast<uint4*>(p + h0) = pack8bf(r.v[c]);
   }
 }
 
@@ -84,7 +54,7 @@ template <int NCH>
 static __device__ __forceinline__ void load_row_f32(const float* __restrict__ p, int H, int lane, RowF<NCH>& r) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const int h0 = (lane + 64 * c) * 8;
+    const int h0 = ln_col(lane, c);
     if (h0 < H) {
       const float4 a = *reinterpret_cast<const float4*>(p + h0);
       const float4 b = *reinterpret_cast<const float4*>(p + h0 + 4);
@@ -103,7 +73,7 @@ static __device__ __forceinline__ void load_colkeys(uint32_t seed, int lane, Row
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) k.v[c][j] = __uint_as_float(drop_colkey(seed, (uint32_t)((lane + 64 * c) * 8 + j)));
+    for (int j = 0; j < 8; ++j) k.v[c][j] = __uint_as_float(drop_colkey(seed, (uint32_t)(ln_col(lane, c) + j)));
 }
 template <int NCH>
 static __device__ __forceinline__ void drop_row(RowF<NCH>& x, const RowF<NCH>& ck, uint32_t seed, uint32_t thresh, float scale,
@@ -135,7 +105,7 @@ static __device__ __forceinline__ void row_stats(const RowF<NCH>& x, int H, floa
   float q = 0.0f;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const int h0 = (threadIdx.x % 64 + 64 * c) * 8;
+    const int h0 = ln_col(threadIdx.x % 64, c);
     if (h0 < H) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -146,6 +116,24 @@ static __device__ __forceinline__ void row_stats(const RowF<NCH>& x, int H, floa
   }
   rstd = rsqrtf(wave_sum(q) / (float)H + eps);
 }
+
+// What the three forward kernels end with: x <- LayerNorm(x) * gamma + beta (embed_ln_fwd_kernel applies dropout here), then the row
+// and its statistics are stored.  Macros over the kernel's own NCH, H, eps, lane, g, b, y, mean_o, rstd_o: as inline functions
+// either half changes the instruction stream of all six instantiations.
+#define LN_AFFINE(x, mean, rstd)                                                                                    \
+  do {                                                                                                              \
+    row_stats<NCH>(x, H, eps, mean, rstd);                                                                          \
+    _Pragma("unroll") for (int c = 0; c < NCH; ++c)                                                                 \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) x.v[c][j] = (x.v[c][j] - mean) * rstd * g.v[c][j] + b.v[c][j];    \
+  } while (0)
+#define LN_STORE(r, x, mean, rstd)                      \
+  do {                                                  \
+    store_row_bf16<NCH>(y + (size_t)r * H, H, lane, x); \
+    if (lane == 0) {                                    \
+      mean_o[r] = mean;                                 \
+      rstd_o[r] = rstd;                                 \
+    }                                                   \
+  } while (0)
 
 template <int NCH>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ h, const float* __restrict__ gamma,
@@ -167,16 +155,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
     RowF<NCH> x;
     unpack_row<NCH>(raw, x);
     float mean, rstd;
-    row_stats<NCH>(x, H, eps, mean, rstd);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x.v[c][j] = (x.v[c][j] - mean) * rstd * g.v[c][j] + b.v[c][j];
-    store_row_bf16<NCH>(y + (size_t)r * H, H, lane, x);
-    if (lane == 0) {
-      mean_o[r] = mean;
-      rstd_o[r] = rstd;
-    }
+    LN_AFFINE(x, mean, rstd);
+    LN_STORE(r, x, mean, rstd);
     raw = nxt;
   }
 }
@@ -199,9 +179,11 @@ __global__ __launch_bounds__(256) void ln_fwd_slabs_kernel(const float* __restri
   load_row_f32<NCH>(beta, H, lane, b);
   for (int r = wave; r < M; r += nwave) {
     RowRaw<NCH> raw;
+    // (the fold loop is also in ln_bwd_kernel's load_dy, in another spelling: either kernel's instruction stream follows its own, so
+    // a shared load_row_slabs -- inline function or macro, the row stored here or after the loop -- changes one of the two)
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const int h0 = (lane + 64 * c) * 8;
+      const int h0 = ln_col(lane, c);
       raw.v[c] = make_uint4(0u, 0u, 0u, 0u);
       if (h0 < H) {
         raw.v[c] = splitk_fold8_pack(ws, splits, slab, bias, addend, ldadd, r, h0, H, drop_seed, drop_thresh);
@@ -211,16 +193,8 @@ __global__ __launch_bounds__(256) void ln_fwd_slabs_kernel(const float* __restri
     RowF<NCH> x;
     unpack_row<NCH>(raw, x);
     float mean, rstd;
-    row_stats<NCH>(x, H, eps, mean, rstd);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x.v[c][j] = (x.v[c][j] - mean) * rstd * g.v[c][j] + b.v[c][j];
-    store_row_bf16<NCH>(y + (size_t)r * H, H, lane, x);
-    if (lane == 0) {
-      mean_o[r] = mean;
-      rstd_o[r] = rstd;
-    }
+    LN_AFFINE(x, mean, rstd);
+    LN_STORE(r, x, mean, rstd);
   }
 }
 
@@ -253,17 +227,9 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int* __restrict
     round_row<NCH>(x);
     store_row_bf16<NCH>(h0 + (size_t)r * H, H, lane, x);
     float mean, rstd;
-    row_stats<NCH>(x, H, eps, mean, rstd);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x.v[c][j] = (x.v[c][j] - mean) * rstd * g.v[c][j] + b.v[c][j];
+    LN_AFFINE(x, mean, rstd);
     if (drop_thresh) drop_row<NCH>(x, ck, drop_seed, drop_thresh, dscale, r);  // BertEmbeddings.dropout
-    store_row_bf16<NCH>(y + (size_t)r * H, H, lane, x);
-    if (lane == 0) {
-      mean_o[r] = mean;
-      rstd_o[r] = rstd;
-    }
+    LN_STORE(r, x, mean, rstd);
   }
 }
 
@@ -276,7 +242,7 @@ static __device__ __forceinline__ void flush_row_atomic(float* __restrict__ dst,
                                                         float* __restrict__ stage) {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    float4* s4 = reinterpret_cast<float4*>(stage + (lane + 64 * c) * 8);
+    float4* s4 = reinterpret_cast<float4*>(stage + ln_col(lane, c));
     s4[0] = make_float4(r.v[c][0], r.v[c][1], r.v[c][2], r.v[c][3]);
     s4[1] = make_float4(r.v[c][4], r.v[c][5], r.v[c][6], r.v[c][7]);
   }
@@ -302,9 +268,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                                                      const int* __restrict__ pos_ids, float* __restrict__ dword,
                                                      float* __restrict__ dpos, float* __restrict__ ws, int M, int H,
                                                      bf16_t* __restrict__ dhm, uint32_t drop_seed, uint32_t drop_thresh,
-                                                     const float* __restrict__ dy_ws = nullptr, int dy_splits = 0,
-                                                     const bf16_t* __restrict__ dy_add = nullptr, int dy_ldadd = 0,
-                                                     unsigned char* __restrict__ row_flags = nullptr) {
+                                                     const float* __restrict__ dy_ws, int dy_splits,
+                                                     const bf16_t* __restrict__ dy_add, int dy_ldadd,
+                                                     unsigned char* __restrict__ row_flags) {
   // SLABS (round 6, small micro-batches; a separate instantiation, the other one is untouched): the incoming gradient row is folded from the split-K slabs of the GEMM that
   // produced it -- bf16(sum_s dy_ws[s] + dy_add), kbner_splitk_finish's bits (splitk_fold8_pack) -- instead of read from `dy`.
   // Dropout replay (drop_thresh != 0): EMBED -> the incoming dy is masked first (y = drop(LN(h0)));
@@ -336,7 +302,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     } else {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        const int h0 = (lane + 64 * c) * 8;
+        const int h0 = ln_col(lane, c);
         out.v[c] = (h0 < H) ? splitk_fold8_pack(dy_ws, dy_splits, dy_slab, nullptr, dy_add, dy_ldadd, row, h0, H, 0u, 0u)
                             : make_uint4(0u, 0u, 0u, 0u);
       }
@@ -364,7 +330,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const int h0 = (lane + 64 * c) * 8;
+      const int h0 = ln_col(lane, c);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xh = (h0 < H) ? (x.v[c][j] - mean) * rstd : 0.0f;
@@ -425,7 +391,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int col = (lane + 64 * c) * 8 + j;  // < 64*8*NCH
+      const int col = ln_col(lane, c) + j;  // < 64*8*NCH
       red[0][wid][col] = ag.v[c][j];
       red[1][wid][col] = ab.v[c][j];
       red[2][wid][col] = ah.v[c][j];
@@ -442,25 +408,28 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 // out_k[col] += sum_blocks ws[block][k][col], k = 0..2 (dgamma, dbeta, dbias).  grid = (ceil(3H/64), 8): a block owns 64
 // consecutive entries of the 3H-wide partial row and one eighth of the partial rows; 4 row-groups of threads x 8-way
 // unrolled loads keep ~32 loads in flight per thread-column, the 8 slices meet through one atomic per entry.
+// One body for the two kernels below.  A macro (over the kernel's H): the batched kernel reads its outputs' addresses where they are
+// used and the plain one has them as __restrict__ arguments, and no inline function gave both kernels their instruction streams.
+#define LN_COLREDUCE_BODY(ws, nblocks, dgamma, dbeta, dbias)                                                    \
+  __shared__ float red[4][64];                                                                                  \
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;                                                       \
+  const int i = blockIdx.x * 64 + tx; /* over 3*H */                                                            \
+  const int per = (nblocks + gridDim.y - 1) / gridDim.y;                                                        \
+  const int b0 = blockIdx.y * per, b1 = min(nblocks, b0 + per);                                                 \
+  float acc = 0.0f;                                                                                             \
+  if (i < 3 * H) {                                                                                              \
+    _Pragma("unroll 8") for (int b = b0 + ty; b < b1; b += 4) acc += ws[(size_t)b * 3 * H + i];                 \
+  }                                                                                                             \
+  red[ty][tx] = acc;                                                                                            \
+  __syncthreads();                                                                                              \
+  if (ty == 0 && i < 3 * H) {                                                                                   \
+    const int k = i / H, col = i % H;                                                                           \
+    float* out = k == 0 ? dgamma : (k == 1 ? dbeta : dbias);                                                    \
+    if (out != nullptr) atomicAdd(out + col, (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));            \
+  }
 __global__ __launch_bounds__(256) void ln_colreduce_kernel(const float* __restrict__ ws, int nblocks, int H, float* __restrict__ dgamma,
                                                            float* __restrict__ dbeta, float* __restrict__ dbias) {
-  __shared__ float red[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;  // over 3*H
-  const int per = (nblocks + gridDim.y - 1) / gridDim.y;
-  const int b0 = blockIdx.y * per, b1 = min(nblocks, b0 + per);
-  float acc = 0.0f;
-  if (i < 3 * H) {
-#pragma unroll 8
-    for (int b = b0 + ty; b < b1; b += 4) acc += ws[(size_t)b * 3 * H + i];
-  }
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && i < 3 * H) {
-    const int k = i / H, col = i % H;
-    float* out = k == 0 ? dgamma : (k == 1 ? dbeta : dbias);
-    if (out != nullptr) atomicAdd(out + col, (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
-  }
+  LN_COLREDUCE_BODY(ws, nblocks, dgamma, dbeta, dbias)
 }
 
 // The same reduction for up to LN_BATCH_MAX LayerNorms in ONE launch (blockIdx.z picks the item): with a few sentences per step
@@ -478,35 +447,61 @@ struct LnPartialBatch {
   LnPartialItem it[LN_BATCH_MAX];
 };
 __global__ __launch_bounds__(256) void ln_colreduce_batched_kernel(const LnPartialBatch batch, int H) {
-  __shared__ float red[4][64];
   const LnPartialItem& q = batch.it[blockIdx.z];
   const float* __restrict__ ws = q.ws;
   const int nblocks = (int)q.nblocks;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;  // over 3*H
-  const int per = (nblocks + gridDim.y - 1) / gridDim.y;
-  const int b0 = blockIdx.y * per, b1 = min(nblocks, b0 + per);
-  float acc = 0.0f;
-  if (i < 3 * H) {
-#pragma unroll 8
-    for (int b = b0 + ty; b < b1; b += 4) acc += ws[(size_t)b * 3 * H + i];
-  }
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && i < 3 * H) {
-    const int k = i / H, col = i % H;
-    float* out = k == 0 ? q.dgamma : (k == 1 ? q.dbeta : q.dbias);
-    if (out != nullptr) atomicAdd(out + col, (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
-  }
+  LN_COLREDUCE_BODY(ws, nblocks, q.dgamma, q.dbeta, q.dbias)
 }
 
-#define LN_BWD_MAXBLOCKS 1024
+// ---- host side
+
+#define LN_MAXBLOCKS 1024      // grid of every row kernel here
+#define LN_BWD_MAXBLOCKS 1024  // partial rows (3 H floats each) that a backward workspace holds
+
+static inline bool ln_args_ok(int M, int H) { return M >= 0 && H > 0 && H % 8 == 0 && H <= LN_MAXH; }
 
 static inline int ln_grid(int M) {
   int g = (M + 3) / 4;
-  if (g > 1024) g = 1024;
+  if (g > LN_MAXBLOCKS) g = LN_MAXBLOCKS;
   if (g < 1) g = 1;
   return g;
+}
+// a backward block leaves one partial row: ln_grid's own cap keeps them inside the workspace, no second clamp is needed
+static_assert(LN_MAXBLOCKS <= LN_BWD_MAXBLOCKS, "ln_bwd_kernel's grid must fit kbner_ln_bwd_ws_floats");
+static inline int ln_bwd_grid(int M) { return ln_grid(M); }
+
+// Launches KERNEL, an instantiation written in terms of NCH: the chunks per lane that cover H (ln_args_ok: at most LN_MAXCH)
+#define LN_LAUNCH(KERNEL, H, grid, stream, ...)                                                  \
+  do {                                                                                           \
+    static_assert(LN_MAXCH == 2, "one branch per chunk count");                                  \
+    if ((H) <= 64 * 8) {                                                                         \
+      constexpr int NCH = 1;                                                                     \
+      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
+    } else {                                                                                     \
+      constexpr int NCH = 2;                                                                     \
+      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);  \
+    }                                                                                            \
+  } while (0)
+
+static inline void launch_colreduce(const float* ws, int nblocks, int H, float* dgamma, float* dbeta, float* dbias, void* stream) {
+  hipLaunchKernelGGL(ln_colreduce_kernel, dim3((3 * H + 63) / 64, 8), dim3(256), 0, (hipStream_t)stream, ws, nblocks, H, dgamma, dbeta,
+                     dbias);
+}
+
+// The one backward launch (kbner_ln_bwd, kbner_ln_bwd_slabs, kbner_embed_ln_bwd[_mark]): the arguments are ln_bwd_kernel's.
+// dgamma == NULL: the partial rows stay in ws -- kbner_ln_bwd_blocks(M) of them -- for kbner_ln_colreduce_batched.
+template <bool EMBED, bool SLABS>
+static int ln_bwd_launch(const bf16_t* dy, const bf16_t* h, const float* mean, const float* rstd, const float* gamma, bf16_t* dh,
+                         float* dgamma, float* dbeta, float* dbias, const int* ids, const int* pos_ids, float* dword, float* dpos,
+                         float* ws, int M, int H, bf16_t* dhm, uint32_t drop_seed, uint32_t drop_thresh, const float* dy_ws,
+                         int dy_splits, const bf16_t* dy_add, int dy_ldadd, unsigned char* row_flags, void* stream) {
+  KBNER_CHECK_ARG(ln_args_ok(M, H) && ws != nullptr);
+  if (M == 0) return 0;
+  const int grid = ln_bwd_grid(M);
+  LN_LAUNCH((ln_bwd_kernel<NCH, EMBED, SLABS>), H, grid, stream, dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias, ids, pos_ids, dword,
+            dpos, ws, M, H, dhm, drop_seed, drop_thresh, dy_ws, dy_splits, dy_add, dy_ldadd, row_flags);
+  if (dgamma != nullptr) launch_colreduce(ws, grid, H, dgamma, dbeta, dbias, stream);
+  KBNER_LAUNCH_RET();
 }
 
 extern "C" {
@@ -515,26 +510,19 @@ int kbner_ln_bwd_ws_floats(int H) { return LN_BWD_MAXBLOCKS * 3 * H; }
 
 int kbner_ln_fwd(const bf16_t* h, const float* gamma, const float* beta, float eps, bf16_t* y, float* mean, float* rstd,
                  int M, int H, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH);
+  KBNER_CHECK_ARG(ln_args_ok(M, H));
   if (M == 0) return 0;
-  if (H <= 512)
-    hipLaunchKernelGGL(ln_fwd_kernel<1>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, h, gamma, beta, eps, y, mean, rstd, M, H);
-  else
-    hipLaunchKernelGGL(ln_fwd_kernel<2>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, h, gamma, beta, eps, y, mean, rstd, M, H);
+  LN_LAUNCH(ln_fwd_kernel<NCH>, H, ln_grid(M), stream, h, gamma, beta, eps, y, mean, rstd, M, H);
   KBNER_LAUNCH_RET();
 }
 
 int kbner_embed_ln_fwd(const int* ids, const int* pos_ids, const float* word, const float* pos, const float* type0,
                        const float* gamma, const float* beta, float eps, bf16_t* h0, bf16_t* y, float* mean, float* rstd,
                        int M, int H, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH);
+  KBNER_CHECK_ARG(ln_args_ok(M, H));
   if (M == 0) return 0;
-  if (H <= 512)
-    hipLaunchKernelGGL(embed_ln_fwd_kernel<1>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, ids, pos_ids, word, pos,
-                       type0, gamma, beta, eps, h0, y, mean, rstd, M, H, drop_seed, drop_thresh);
-  else
-    hipLaunchKernelGGL(embed_ln_fwd_kernel<2>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, ids, pos_ids, word, pos,
-                       type0, gamma, beta, eps, h0, y, mean, rstd, M, H, drop_seed, drop_thresh);
+  LN_LAUNCH(embed_ln_fwd_kernel<NCH>, H, ln_grid(M), stream, ids, pos_ids, word, pos, type0, gamma, beta, eps, h0, y, mean, rstd, M, H,
+            drop_seed, drop_thresh);
   KBNER_LAUNCH_RET();
 }
 
@@ -544,22 +532,9 @@ int kbner_embed_ln_fwd(const int* ids, const int* pos_ids, const float* word, co
 int kbner_ln_bwd(const bf16_t* dy, const bf16_t* h, const float* mean, const float* rstd, const float* gamma, bf16_t* dh,
                  float* dgamma, float* dbeta, float* dbias, float* ws, int M, int H, bf16_t* dhm, uint32_t drop_seed,
                  uint32_t drop_thresh, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH && ws != nullptr);
   KBNER_CHECK_ARG(drop_thresh == 0 || dhm != nullptr);
-  if (M == 0) return 0;
-  int grid = ln_grid(M);
-  if (grid > LN_BWD_MAXBLOCKS) grid = LN_BWD_MAXBLOCKS;
-  if (H <= 512)
-    hipLaunchKernelGGL((ln_bwd_kernel<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, h, mean, rstd, gamma, dh,
-                       dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm, drop_seed, drop_thresh);
-  else
-    hipLaunchKernelGGL((ln_bwd_kernel<2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, h, mean, rstd, gamma, dh,
-                       dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm, drop_seed, drop_thresh);
-  // (dgamma == NULL: the partial rows stay in ws -- kbner_ln_bwd_blocks(M) of them -- for kbner_ln_colreduce_batched)
-  if (dgamma != nullptr)
-    hipLaunchKernelGGL(ln_colreduce_kernel, dim3((3 * H + 63) / 64, 8), dim3(256), 0, (hipStream_t)stream, ws, grid, H, dgamma, dbeta,
-                       dbias);
-  KBNER_LAUNCH_RET();
+  return ln_bwd_launch<false, false>(dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm,
+                                     drop_seed, drop_thresh, nullptr, 0, nullptr, 0, nullptr, stream);
 }
 
 // kbner_ln_fwd / kbner_ln_bwd with the input row folded from split-K slabs (ws f32 [splits][M, H]) instead of read as bf16: what
@@ -567,45 +542,25 @@ int kbner_ln_bwd(const bf16_t* dy, const bf16_t* h, const float* mean, const flo
 int kbner_ln_fwd_slabs(const float* ws, int splits, const float* bias, const bf16_t* addend, int ldadd, uint32_t drop_seed,
                        uint32_t drop_thresh, bf16_t* h, const float* gamma, const float* beta, float eps, bf16_t* y, float* mean,
                        float* rstd, int M, int H, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH && ws != nullptr && splits >= 1 && splits <= 16);
+  KBNER_CHECK_ARG(ln_args_ok(M, H) && ws != nullptr && splits >= 1 && splits <= 16);
   KBNER_CHECK_ARG(h != nullptr && y != nullptr && (addend == nullptr || ldadd % 8 == 0));
   if (M == 0) return 0;
-  if (H <= 512)
-    hipLaunchKernelGGL(ln_fwd_slabs_kernel<1>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, ws, splits, bias, addend, ldadd,
-                       drop_seed, drop_thresh, h, gamma, beta, eps, y, mean, rstd, M, H);
-  else
-    hipLaunchKernelGGL(ln_fwd_slabs_kernel<2>, dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, ws, splits, bias, addend, ldadd,
-                       drop_seed, drop_thresh, h, gamma, beta, eps, y, mean, rstd, M, H);
+  LN_LAUNCH(ln_fwd_slabs_kernel<NCH>, H, ln_grid(M), stream, ws, splits, bias, addend, ldadd, drop_seed, drop_thresh, h, gamma, beta, eps,
+            y, mean, rstd, M, H);
   KBNER_LAUNCH_RET();
 }
 
 int kbner_ln_bwd_slabs(const float* dy_ws, int splits, const bf16_t* dy_add, int ldadd, const bf16_t* h, const float* mean,
                        const float* rstd, const float* gamma, bf16_t* dh, float* dgamma, float* dbeta, float* dbias, float* ws, int M,
                        int H, bf16_t* dhm, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH && ws != nullptr && dy_ws != nullptr);
-  KBNER_CHECK_ARG(splits >= 1 && splits <= 16 && (dy_add == nullptr || ldadd % 8 == 0) && (drop_thresh == 0 || dhm != nullptr));
-  if (M == 0) return 0;
-  int grid = ln_grid(M);
-  if (grid > LN_BWD_MAXBLOCKS) grid = LN_BWD_MAXBLOCKS;
-  if (H <= 512)
-    hipLaunchKernelGGL((ln_bwd_kernel<1, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)nullptr, h, mean, rstd,
-                       gamma, dh, dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm, drop_seed, drop_thresh, dy_ws,
-                       splits, dy_add, ldadd);
-  else
-    hipLaunchKernelGGL((ln_bwd_kernel<2, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)nullptr, h, mean, rstd,
-                       gamma, dh, dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm, drop_seed, drop_thresh, dy_ws,
-                       splits, dy_add, ldadd);
-  if (dgamma != nullptr)
-    hipLaunchKernelGGL(ln_colreduce_kernel, dim3((3 * H + 63) / 64, 8), dim3(256), 0, (hipStream_t)stream, ws, grid, H, dgamma, dbeta,
-                       dbias);
-  KBNER_LAUNCH_RET();
+  KBNER_CHECK_ARG(dy_ws != nullptr && splits >= 1 && splits <= 16 && (dy_add == nullptr || ldadd % 8 == 0));
+  KBNER_CHECK_ARG(drop_thresh == 0 || dhm != nullptr);
+  return ln_bwd_launch<false, true>(nullptr, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H,
+                                    dhm, drop_seed, drop_thresh, dy_ws, splits, dy_add, ldadd, nullptr, stream);
 }
 
 // how many partial rows (of 3 H floats) kbner_ln_bwd leaves in its workspace for M rows
-int kbner_ln_bwd_blocks(int M) {
-  int grid = ln_grid(M);
-  return grid > LN_BWD_MAXBLOCKS ? LN_BWD_MAXBLOCKS : grid;
-}
+int kbner_ln_bwd_blocks(int M) { return ln_bwd_grid(M); }
 
 // items (HOST memory, n <= 64 records of 5 x 64 bits: ws, dgamma, dbeta, dbias -- device pointers, dbias may be 0 -- and the number of
 // partial rows): dgamma / dbeta / dbias += the column sums of each item's partial rows, all in one launch.
@@ -626,34 +581,11 @@ int kbner_ln_colreduce_batched(const long long* items, int n, int H, void* strea
   KBNER_LAUNCH_RET();
 }
 
-static int embed_ln_bwd_impl(const bf16_t* dy, const bf16_t* h0, const float* mean, const float* rstd, const float* gamma,
-                             const int* ids, const int* pos_ids, float* dgamma, float* dbeta, float* dword, float* dpos,
-                             float* dtype0, float* ws, int M, int H, uint32_t drop_seed, uint32_t drop_thresh, unsigned char* row_flags,
-                             void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && H > 0 && H % 8 == 0 && H <= 64 * 8 * LN_MAXCH && ws != nullptr);
-  if (M == 0) return 0;
-  int grid = ln_grid(M);
-  if (grid > LN_BWD_MAXBLOCKS) grid = LN_BWD_MAXBLOCKS;
-  if (H <= 512)
-    hipLaunchKernelGGL((ln_bwd_kernel<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, h0, mean, rstd, gamma,
-                       (bf16_t*)nullptr, dgamma, dbeta, dtype0, ids, pos_ids, dword, dpos, ws, M, H, (bf16_t*)nullptr, drop_seed,
-                       drop_thresh, (const float*)nullptr, 0, (const bf16_t*)nullptr, 0, row_flags);
-  else
-    hipLaunchKernelGGL((ln_bwd_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, h0, mean, rstd, gamma,
-                       (bf16_t*)nullptr, dgamma, dbeta, dtype0, ids, pos_ids, dword, dpos, ws, M, H, (bf16_t*)nullptr, drop_seed,
-                       drop_thresh, (const float*)nullptr, 0, (const bf16_t*)nullptr, 0, row_flags);
-  // (dgamma == NULL: the partial rows stay in ws for kbner_ln_colreduce_batched, as for kbner_ln_bwd)
-  if (dgamma != nullptr)
-    hipLaunchKernelGGL(ln_colreduce_kernel, dim3((3 * H + 63) / 64, 8), dim3(256), 0, (hipStream_t)stream, ws, grid, H, dgamma, dbeta,
-                       dtype0);
-  KBNER_LAUNCH_RET();
-}
-
 int kbner_embed_ln_bwd(const bf16_t* dy, const bf16_t* h0, const float* mean, const float* rstd, const float* gamma,
                        const int* ids, const int* pos_ids, float* dgamma, float* dbeta, float* dword, float* dpos,
                        float* dtype0, float* ws, int M, int H, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
-  return embed_ln_bwd_impl(dy, h0, mean, rstd, gamma, ids, pos_ids, dgamma, dbeta, dword, dpos, dtype0, ws, M, H, drop_seed, drop_thresh,
-                           nullptr, stream);
+  return ln_bwd_launch<true, false>(dy, h0, mean, rstd, gamma, nullptr, dgamma, dbeta, dtype0, ids, pos_ids, dword, dpos, ws, M, H, nullptr,
+                                    drop_seed, drop_thresh, nullptr, 0, nullptr, 0, nullptr, stream);
 }
 
 // the same + the optimizer's embedding-row flags set by the kernel itself (row_flags u8[rows of dword], may be NULL): every row this
@@ -662,8 +594,8 @@ int kbner_embed_ln_bwd_mark(const bf16_t* dy, const bf16_t* h0, const float* mea
                             const int* ids, const int* pos_ids, float* dgamma, float* dbeta, float* dword, float* dpos,
                             float* dtype0, float* ws, unsigned char* row_flags, int M, int H, uint32_t drop_seed, uint32_t drop_thresh,
                             void* stream) {
-  return embed_ln_bwd_impl(dy, h0, mean, rstd, gamma, ids, pos_ids, dgamma, dbeta, dword, dpos, dtype0, ws, M, H, drop_seed, drop_thresh,
-                           row_flags, stream);
+  return ln_bwd_launch<true, false>(dy, h0, mean, rstd, gamma, nullptr, dgamma, dbeta, dtype0, ids, pos_ids, dword, dpos, ws, M, H, nullptr,
+                                    drop_seed, drop_thresh, nullptr, 0, nullptr, 0, row_flags, stream);
 }
 
 }  // extern "C"

@@ -11,17 +11,33 @@
 //   step_size = lr * sqrt(1-b2^t) / (1-b1^t) is computed on the host in double and passed in.
 #include "common.h"
 
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n,
-                                                    size_t n_shadow, float step_size, float lr_wd, float b1, float b2, float eps,
-                                                    const float* __restrict__ gnorm_sq, float max_norm, float grad_scale,
-                                                    int zero_grad) {
+// grad_scale times clip_grad_norm_'s coefficient max_norm / (norm + 1e-6) where that is below 1 (gnorm_sq NULL: no clipping)
+static __device__ __forceinline__ float clipped_grad_scale(const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
   float gs = grad_scale;
   if (gnorm_sq) {
     const float norm = sqrtf(*gnorm_sq) * grad_scale;
     const float coef = max_norm / (norm + 1e-6f);
     if (coef < 1.0f) gs *= coef;
   }
+  return gs;
+}
+// The AdamW update of one element (weight decay apart) with the gradient g * gs, over the kernel's b1, b2, eps, step_size.  A macro
+// that pastes the statements: HIP contracts a * b + c * d into one fma, and which product it fuses follows how the expression reaches
+// the compiler -- as an inline function the three kernels round m differently, and lazy rows no longer equal eager rows bit for bit.
+#define ADAM_STEP(p, g, m, v)                     \
+  do {                                            \
+    const float gk = (g) * gs;                    \
+    m = m * b1 + (1.0f - b1) * gk;                \
+    v = v * b2 + (1.0f - b2) * gk * gk;           \
+    p -= step_size * (m / (sqrtf(v) + eps));      \
+  } while (0)
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n,
+                                                    size_t n_shadow, float step_size, float lr_wd, float b1, float b2, float eps,
+                                                    const float* __restrict__ gnorm_sq, float max_norm, float grad_scale,
+                                                    int zero_grad) {
+  const float gs = clipped_grad_scale(gnorm_sq, max_norm, grad_scale);
   const size_t n4 = n / 4;
   // Each workgroup walks CONTIGUOUS chunks of ADAMW_CHUNK float4 per array: it touches 16 consecutive KiB of each of the eight
   // streams before it moves on, instead of 4 KiB per grid stride.  Round 5, tools/adamw_bench.py,
@@ -41,10 +57,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     float* va = &vv.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float gk = ga[k] * gs;
-      ma[k] = ma[k] * b1 + (1.0f - b1) * gk;
-      va[k] = va[k] * b2 + (1.0f - b2) * gk * gk;
-      pa[k] -= step_size * (ma[k] / (sqrtf(va[k]) + eps));
+      ADAM_STEP(pa[k], ga[k], ma[k], va[k]);
       if (lr_wd != 0.0f) pa[k] -= lr_wd * pa[k];
     }
     reinterpret_cast<float4*>(p)[i] = pp;
@@ -80,12 +93,7 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ p, 
   const unsigned fl = __builtin_amdgcn_readfirstlane((unsigned)flags[row]);
   if (!fl) return;
   const bool touched = (fl & 2u) != 0;
-  float gs = grad_scale;
-  if (gnorm_sq) {
-    const float norm = sqrtf(*gnorm_sq) * grad_scale;
-    const float coef = max_norm / (norm + 1e-6f);
-    if (coef < 1.0f) gs *= coef;
-  }
+  const float gs = clipped_grad_scale(gnorm_sq, max_norm, grad_scale);
   const size_t base = (size_t)row * width;
   for (int i = (threadIdx.x & 63) * 4; i < width; i += 256) {
     float4 pp = *reinterpret_cast<float4*>(p + base + i);
@@ -97,12 +105,7 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(float* __restrict__ p, 
     float* ma = &mm.x;
     float* va = &vv.x;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gk = ga[k] * gs;
-      ma[k] = ma[k] * b1 + (1.0f - b1) * gk;
-      va[k] = va[k] * b2 + (1.0f - b2) * gk * gk;
-      pa[k] -= step_size * (ma[k] / (sqrtf(va[k]) + eps));
-    }
+    for (int k = 0; k < 4; ++k) ADAM_STEP(pa[k], ga[k], ma[k], va[k]);
     *reinterpret_cast<float4*>(p + base + i) = pp;
     *reinterpret_cast<float4*>(m + base + i) = mm;
     *reinterpret_cast<float4*>(v + base + i) = vv;
@@ -132,26 +135,23 @@ __device__ __forceinline__ void adam_zero_grad_step(float& p, float& m, float& v
   p -= step * (m / (sqrtf(v) + eps));
 }
 
-// one wave: the zero-gradient updates of steps (from, to] on one row of width <= 1024 held in registers
-template <int NV>
+// one wave: one row of width <= 1024 loaded into registers, then the zero-gradient updates of steps (from, to] on it
 __device__ __forceinline__ void row_catch_up(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, size_t base, int width,
                                              int lane, int from, int to, const float* __restrict__ hist, int mask, float b1, float b2,
-                                             float eps, RowState& st, bool load) {
-  if (load) {
+                                             float eps, RowState& st) {
 #pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      const int i = lane * 4 + c * 256;
-      if (i < width) {
-        st.p[c] = *reinterpret_cast<const float4*>(p + base + i);
-        st.m[c] = *reinterpret_cast<const float4*>(m + base + i);
-        st.v[c] = *reinterpret_cast<const float4*>(v + base + i);
-      }
+  for (int c = 0; c < 4; ++c) {
+    const int i = lane * 4 + c * 256;
+    if (i < width) {
+      st.p[c] = *reinterpret_cast<const float4*>(p + base + i);
+      st.m[c] = *reinterpret_cast<const float4*>(m + base + i);
+      st.v[c] = *reinterpret_cast<const float4*>(v + base + i);
     }
   }
   for (int s = from + 1; s <= to; ++s) {
     const float step = hist[s & mask];
 #pragma unroll
-    for (int c = 0; c < NV; ++c) {
+    for (int c = 0; c < 4; ++c) {
       adam_zero_grad_step(st.p[c].x, st.m[c].x, st.v[c].x, step, b1, b2, eps);
       adam_zero_grad_step(st.p[c].y, st.m[c].y, st.v[c].y, step, b1, b2, eps);
       adam_zero_grad_step(st.p[c].z, st.m[c].z, st.v[c].z, step, b1, b2, eps);
@@ -160,11 +160,10 @@ __device__ __forceinline__ void row_catch_up(float* __restrict__ p, float* __res
   }
 }
 
-template <int NV>
 __device__ __forceinline__ void row_store(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, size_t base, int width,
                                           int lane, const RowState& st) {
 #pragma unroll
-  for (int c = 0; c < NV; ++c) {
+  for (int c = 0; c < 4; ++c) {
     const int i = lane * 4 + c * 256;
     if (i < width) {
       *reinterpret_cast<float4*>(p + base + i) = st.p[c];
@@ -237,16 +236,11 @@ __global__ __launch_bounds__(256) void adamw_rows_lazy_kernel(float* __restrict_
   if (row >= rows) return;
   const unsigned fl = __builtin_amdgcn_readfirstlane((unsigned)flags[row]);
   if (!(fl & 2u)) return;
-  float gs = grad_scale;
-  if (gnorm_sq) {
-    const float norm = sqrtf(*gnorm_sq) * grad_scale;
-    const float coef = max_norm / (norm + 1e-6f);
-    if (coef < 1.0f) gs *= coef;
-  }
+  const float gs = clipped_grad_scale(gnorm_sq, max_norm, grad_scale);
   const size_t base = (size_t)row * width;
   const int from = __builtin_amdgcn_readfirstlane(row_t[row]);
   RowState st;
-  row_catch_up<4>(p, m, v, base, width, lane, from < 0 ? t - 1 : from, t - 1, hist, mask, b1, b2, eps, st, true);
+  row_catch_up(p, m, v, base, width, lane, from < 0 ? t - 1 : from, t - 1, hist, mask, b1, b2, eps, st);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int i = lane * 4 + c * 256;
@@ -257,16 +251,11 @@ __global__ __launch_bounds__(256) void adamw_rows_lazy_kernel(float* __restrict_
       float* ma = &st.m[c].x;
       float* va = &st.v[c].x;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gk = ga[k] * gs;
-        ma[k] = ma[k] * b1 + (1.0f - b1) * gk;
-        va[k] = va[k] * b2 + (1.0f - b2) * gk * gk;
-        pa[k] -= step_size * (ma[k] / (sqrtf(va[k]) + eps));
-      }
+      for (int k = 0; k < 4; ++k) ADAM_STEP(pa[k], ga[k], ma[k], va[k]);
       *reinterpret_cast<float4*>(g + base + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
-  row_store<4>(p, m, v, base, width, lane, st);
+  row_store(p, m, v, base, width, lane, st);
   if (lane == 0) {
     row_t[row] = t;
     flags[row] = (unsigned char)(fl & ~2u);
@@ -278,10 +267,20 @@ __global__ void rows_clock_kernel(int* __restrict__ clock, float* __restrict__ h
   *clock = t;
 }
 
+// partial[blockIdx.x] = the sum of acc over the block's 256 threads: wave_sum, the four waves' sums through LDS, thread 0 writes.
+// (A macro: as an inline function it moves two instructions of both kernels that use it.)
+#define BLOCK_SUM_TO_PARTIAL(acc, partial)                                                    \
+  do {                                                                                        \
+    __shared__ float red[4];                                                                  \
+    acc = wave_sum(acc);                                                                      \
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;                                 \
+    __syncthreads();                                                                          \
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);        \
+  } while (0)
+
 // partial[b] = sum of g^2 over the TOUCHED rows among [b * rpb, (b+1) * rpb)
 __global__ __launch_bounds__(256) void sqnorm_rows_kernel(const float* __restrict__ g, const unsigned char* __restrict__ flags,
                                                           int rows, int width, int rpb, float* __restrict__ partial) {
-  __shared__ float red[4];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r1 = min(rows, (int)(blockIdx.x + 1) * rpb);
   float acc = 0.0f;
@@ -300,10 +299,7 @@ __global__ __launch_bounds__(256) void sqnorm_rows_kernel(const float* __restric
       }
     }
   }
-  acc = wave_sum(acc);
-  if (lane == 0) red[wid] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  BLOCK_SUM_TO_PARTIAL(acc, partial);
 }
 
 // flags[ids[i]] = LIVE | TOUCHED for i < n (ids < 0 ignored): which embedding rows have ever / now received a gradient
@@ -316,7 +312,6 @@ __global__ __launch_bounds__(256) void mark_rows_kernel(const int* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ partial) {
-  __shared__ float red[4];
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   float acc = 0.0f;
@@ -324,10 +319,7 @@ __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __rest
     const float4 x = reinterpret_cast<const float4*>(g)[i];
     acc += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  BLOCK_SUM_TO_PARTIAL(acc, partial);
 }
 
 __global__ __launch_bounds__(256) void sqnorm_final_kernel(const float* __restrict__ partial, int np, float* __restrict__ out,
@@ -362,12 +354,8 @@ __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const bf16_t* __restri
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const uint2 u = reinterpret_cast<const uint2*>(x)[i];
-    float4 a;
-    a.x = __uint_as_float(u.x << 16);
-    a.y = __uint_as_float(u.x & 0xffff0000u);
-    a.z = __uint_as_float(u.y << 16);
-    a.w = __uint_as_float(u.y & 0xffff0000u);
-    reinterpret_cast<float4*>(y)[i] = a;
+    const f2v lo = unpack2bf(u.x), hi = unpack2bf(u.y);
+    reinterpret_cast<float4*>(y)[i] = make_float4(lo[0], lo[1], hi[0], hi[1]);
   }
 }
 
@@ -382,6 +370,12 @@ __global__ __launch_bounds__(64) void wdiff_sum_kernel(const float* __restrict__
 
 #define SQN_BLOCKS 2048
 
+// blocks of 256 threads for n / 4 float4 elements, at most cap (the kernels stride over the rest)
+static inline unsigned flat4_blocks(size_t n, size_t cap) {
+  const size_t blocks = (n / 4 + 255) / 256;
+  return (unsigned)(blocks > cap ? cap : blocks);
+}
+
 extern "C" {
 
 int kbner_sqnorm_ws_floats(void) { return SQN_BLOCKS; }
@@ -392,9 +386,7 @@ int kbner_adamw_hf(float* p, float* g, float* m, float* v, bf16_t* shadow, size_
                    int zero_grad, void* stream) {
   KBNER_CHECK_ARG(n % 4 == 0 && n_shadow % 4 == 0 && n_shadow <= n);
   if (n == 0) return 0;
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n, n_shadow,
+  hipLaunchKernelGGL(adamw_kernel, dim3(flat4_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n, n_shadow,
                      step_size, lr_wd, b1, b2, eps, gnorm_sq, max_norm, grad_scale, zero_grad);
   KBNER_LAUNCH_RET();
 }
@@ -466,10 +458,9 @@ int kbner_mark_rows(const int* ids, int n, unsigned char* flags, int rows, void*
 // out[0] (+)= sum g^2 ; ws holds kbner_sqnorm_ws_floats() floats
 int kbner_grad_sqnorm(const float* g, size_t n, float* ws, float* out, int accumulate, void* stream) {
   KBNER_CHECK_ARG(n % 4 == 0);
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > SQN_BLOCKS) blocks = SQN_BLOCKS;
+  unsigned blocks = flat4_blocks(n, SQN_BLOCKS);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, ws);
+  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, ws);
   hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, (int)blocks, out, accumulate);
   KBNER_LAUNCH_RET();
 }
@@ -477,18 +468,14 @@ int kbner_grad_sqnorm(const float* g, size_t n, float* ws, float* out, int accum
 int kbner_f32_to_bf16(const float* x, bf16_t* y, size_t n, void* stream) {
   KBNER_CHECK_ARG(n % 4 == 0);
   if (n == 0) return 0;
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, n);
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(flat4_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, n);
   KBNER_LAUNCH_RET();
 }
 
 int kbner_bf16_to_f32(const bf16_t* x, float* y, size_t n, void* stream) {
   KBNER_CHECK_ARG(n % 4 == 0);
   if (n == 0) return 0;
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, n);
+  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(flat4_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, n);
   KBNER_LAUNCH_RET();
 }
 

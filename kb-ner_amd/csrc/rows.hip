@@ -9,7 +9,18 @@
 // gather and compaction are ONE gather), and self.linear (sequence_tagger_model.py:1027).
 #include "common.h"
 
-#define HEAD_MAXT 64
+// wave-per-row kernels: 4 rows per block
+static inline int rows_grid(int R) {
+  int g = (R + 3) / 4;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  return g;
+}
+// one thread per flat index 0..n: blocks of 256
+#define FLAT_LAUNCH(kernel, n, stream, ...) \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(((size_t)(n) + 255) / 256)), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__)
+
+// ---- gather / scatter
 
 // out[r,:] = idx[r] >= 0 ? src[idx[r],:] : 0        (bf16 rows, H % 8 == 0)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restrict__ src, const int* __restrict__ idx,
@@ -42,13 +53,114 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16_t* __restr
   }
 }
 
-static __device__ __forceinline__ void unpack8(const uint4 u, float* f) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-  }
+// fp32 row gather (evaluation path: compaction of the [B*n, T] emissions to the non-S-X rows before Viterbi / CRF loss):
+// out[r,:] = idx[r] >= 0 ? src[idx[r],:] : 0
+__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx,
+                                                              float* __restrict__ out, int R, int W) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= R * W) return;
+  const int r = i / W, c = i % W;
+  const int s = idx[r];
+  out[i] = s >= 0 ? src[(size_t)s * W + c] : 0.0f;
+}
+
+// Strided variant of gather_rows for the stacked-embedding concat of BASELINE config 5 (sequence_tagger_model.py:879-891:
+// torch.cat of every embedding's [B, n, D_i] features): embedding i's pooled rows are written straight into its column block
+// of the concatenated [rows, ld_out] matrix -- out[r, 0:H] = idx[r] >= 0 ? src[idx[r], 0:H] * mul : 0 -- so the concatenation
+// never exists as a separate copy.  16-byte accesses (H % 8 == 0, ld_out % 8 == 0, out 16-byte aligned).
+__global__ __launch_bounds__(256) void gather_rows_ld_kernel(const bf16_t* __restrict__ src, int ld_src, const int* __restrict__ idx,
+                                                             bf16_t* __restrict__ out, int ld_out, int R, int H8) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)R * H8) return;
+  const int r = (int)(i / H8), c = (int)(i % H8);
+  const int s = idx[r];
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (s >= 0) v = *reinterpret_cast<const uint4*>(src + (size_t)s * ld_src + c * 8);
+  *reinterpret_cast<uint4*>(out + (size_t)r * ld_out + c * 8) = v;
+}
+
+// fp32 row scatter (data-parallel exchange of the touched word-embedding gradient rows, kbner/dp.py): dst[idx[r],:] = rows[r,:];
+// indices unique, 16-byte accesses (W % 4 == 0)
+__global__ __launch_bounds__(256) void scatter_rows_f32_kernel(const float4* __restrict__ rows, const int* __restrict__ idx,
+                                                               float4* __restrict__ dst, int R, int W4) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)R * W4) return;
+  const int r = (int)(i / W4), c = (int)(i % W4);
+  const int d = idx[r];
+  if (d >= 0) dst[(size_t)d * W4 + c] = rows[i];
+}
+
+// fp32 row scatter-ADD, any width: dst[idx[r],:] += rows[r,:] for idx[r] >= 0 (indices unique: plain read-modify-write).
+// The knowledge-distillation step (kbner/engine.py:Tagger.kd_loss) folds the gradient of the gold-label NLL, computed on the
+// rows left after the remove_x compaction, back into the gradient of the all-token emissions the KD terms are defined on
+// (the backward of the masked_select compaction, sequence_tagger_model.py:2474-2488, under autograd in the reference).
+__global__ __launch_bounds__(256) void scatter_add_rows_f32_kernel(const float* __restrict__ rows, const int* __restrict__ idx,
+                                                                   float* __restrict__ dst, int R, int W) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)R * W) return;
+  const int r = (int)(i / W), c = (int)(i % W);
+  const int d = idx[r];
+  if (d >= 0) dst[(size_t)d * W + c] += rows[i];
+}
+
+extern "C" {
+int kbner_gather_rows(const bf16_t* src, const int* idx, bf16_t* out, int R, int H, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, src, idx, out, R, H);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_scatter_rows(const bf16_t* dout, const int* idx, bf16_t* dsrc, int R, int H, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_gather_rows_f32(const float* src, const int* idx, float* out, int R, int W, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && W > 0);
+  if (R == 0) return 0;
+  FLAT_LAUNCH(gather_rows_f32_kernel, R * W, stream, src, idx, out, R, W);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_gather_rows_ld(const bf16_t* src, int ld_src, const int* idx, bf16_t* out, int ld_out, int R, int H, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0);
+  if (R == 0) return 0;
+  FLAT_LAUNCH(gather_rows_ld_kernel, (size_t)R * (H / 8), stream, src, ld_src, idx, out, ld_out, R, H / 8);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_scatter_rows_f32(const float* rows, const int* idx, float* dst, int R, int W, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && W > 0 && W % 4 == 0);
+  if (R == 0) return 0;
+  FLAT_LAUNCH(scatter_rows_f32_kernel, (size_t)R * (W / 4), stream, reinterpret_cast<const float4*>(rows), idx,
+              reinterpret_cast<float4*>(dst), R, W / 4);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_scatter_add_rows_f32(const float* rows, const int* idx, float* dst, int R, int W, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && W > 0);
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(rows != nullptr && idx != nullptr && dst != nullptr);
+  FLAT_LAUNCH(scatter_add_rows_f32_kernel, (size_t)R * W, stream, rows, idx, dst, R, W);
+  KBNER_LAUNCH_RET();
+}
+}  // extern "C"
+
+// ---- the emission head
+
+#define HEAD_MAXT 64
+#define HEAD_NCH 2        // 16-byte chunks of a row per lane in the kernels that hold the row in registers
+#define HEAD_MAXH 1024    // the widest row they take
+static_assert(HEAD_MAXH == 64 * 8 * HEAD_NCH, "HEAD_NCH chunks of 64 lanes x 8 columns cover HEAD_MAXH columns");
+
+// sum_j xv[j] * w[j], j = 0..7: ONE expression for the three forward kernels (the same bits from each)
+static __device__ __forceinline__ float head_dot8(const float (&xv)[8], const float* __restrict__ w) {
+  const float4 a = *reinterpret_cast<const float4*>(w);
+  const float4 b = *reinterpret_cast<const float4*>(w + 4);
+  return xv[0] * a.x + xv[1] * a.y + xv[2] * a.z + xv[3] * a.w + xv[4] * b.x + xv[5] * b.y + xv[6] * b.z + xv[7] * b.w;
 }
 
 // emissions: out[r,t] = sum_h x[r,h] * w[t,h] + b[t]    (x bf16, w/b/out fp32; one wave per row)
@@ -59,12 +171,12 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const bf16_t* __restrict_
   const int wave = blockIdx.x * 4 + threadIdx.x / 64;
   const int nwave = gridDim.x * 4;
   for (int r = wave; r < R; r += nwave) {
-    float xv[2][8];
+    float xv[HEAD_NCH][8];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
+    for (int c = 0; c < HEAD_NCH; ++c) {
       const int h0 = (lane + 64 * c) * 8;
       if (h0 < H) {
-        unpack8(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv[c]);
+        unpack8bf(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv[c]);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) xv[c][j] = 0.0f;
@@ -73,14 +185,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const bf16_t* __restrict_
     for (int t = 0; t < T; ++t) {
       float acc = 0.0f;
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
+      for (int c = 0; c < HEAD_NCH; ++c) {
         const int h0 = (lane + 64 * c) * 8;
-        if (h0 < H) {
-          const float4 a = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0);
-          const float4 b = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0 + 4);
-          acc += xv[c][0] * a.x + xv[c][1] * a.y + xv[c][2] * a.z + xv[c][3] * a.w + xv[c][4] * b.x + xv[c][5] * b.y +
-                 xv[c][6] * b.z + xv[c][7] * b.w;
-        }
+        if (h0 < H) acc += head_dot8(xv[c], w + (size_t)t * H + h0);
       }
       acc = wave_sum(acc);
       if (lane == 0) out[(size_t)r * T + t] = acc + bias[t];
@@ -99,19 +206,38 @@ __global__ __launch_bounds__(256) void head_fwd_rt_kernel(const bf16_t* __restri
   const int r = id / T, t = id % T;
   float acc = 0.0f;
 #pragma unroll
-  for (int c = 0; c < 2; ++c) {
+  for (int c = 0; c < HEAD_NCH; ++c) {
     const int h0 = (lane + 64 * c) * 8;
     if (h0 < H) {
       float xv[8];
-      unpack8(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv);
-      const float4 a = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0);
-      const float4 b = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0 + 4);
-      // (the same expression and chunk order as head_fwd_kernel: the same bits)
-      acc += xv[0] * a.x + xv[1] * a.y + xv[2] * a.z + xv[3] * a.w + xv[4] * b.x + xv[5] * b.y + xv[6] * b.z + xv[7] * b.w;
+      unpack8bf(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv);
+      acc += head_dot8(xv, w + (size_t)t * H + h0);  // (and the same chunk order as head_fwd_kernel: the same bits)
     }
   }
   acc = wave_sum(acc);
   if (lane == 0) out[(size_t)r * T + t] = acc + bias[t];
+}
+
+// head_fwd_kernel for wide rows (H > HEAD_MAXH: linear(2 * hidden -> T) behind the BiLSTM): the row is walked in 512-column chunks per tag
+// instead of being held in registers
+__global__ __launch_bounds__(256) void head_fwd_wide_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, float* __restrict__ out, int R,
+                                                            int H, int T) {
+  const int lane = threadIdx.x % 64;
+  const int wave = blockIdx.x * 4 + threadIdx.x / 64;
+  const int nwave = gridDim.x * 4;
+  for (int r = wave; r < R; r += nwave) {
+    for (int t = 0; t < T; ++t) {
+      float acc = 0.0f;
+      for (int h0 = lane * 8; h0 < H; h0 += 512) {
+        float xv[8];
+        unpack8bf(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv);
+        acc += head_dot8(xv, w + (size_t)t * H + h0);
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) out[(size_t)r * T + t] = acc + bias[t];
+    }
+  }
 }
 
 // dx[r,h] = sum_t de[r,t] * w[t,h]        (one wave per row; bf16 out)
@@ -121,15 +247,15 @@ __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restric
   const int wave = blockIdx.x * 4 + threadIdx.x / 64;
   const int nwave = gridDim.x * 4;
   for (int r = wave; r < R; r += nwave) {
-    float acc[2][8];
+    float acc[HEAD_NCH][8];
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
+    for (int c = 0; c < HEAD_NCH; ++c)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[c][j] = 0.0f;
     for (int t = 0; t < T; ++t) {
       const float d = de[(size_t)r * T + t];
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
+      for (int c = 0; c < HEAD_NCH; ++c) {
         const int h0 = (lane + 64 * c) * 8;
         if (h0 < H) {
           const float4 a = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0);
@@ -140,16 +266,9 @@ __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restric
       }
     }
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
+    for (int c = 0; c < HEAD_NCH; ++c) {
       const int h0 = (lane + 64 * c) * 8;
-      if (h0 < H) {
-        uint4 u;
-        u.x = pack2bf(acc[c][0], acc[c][1]);
-        u.y = pack2bf(acc[c][2], acc[c][3]);
-        u.z = pack2bf(acc[c][4], acc[c][5]);
-        u.w = pack2bf(acc[c][6], acc[c][7]);
-        *reinterpret_cast<uint4*>(dx + (size_t)r * H + h0) = u;
-      }
+      if (h0 < H) *reinterpret_cast<uint4*>(dx + (size_t)r * H + h0) = pack8bf(acc[c]);
     }
   }
 }
@@ -199,90 +318,13 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const float* __restric
   }
 }
 
-// out[n] += sum_m x[m,n]   (bf16 in, fp32 atomics out).  Block = 64 column-threads (16-byte loads, 512 columns)
-// x 4 row-threads; the 4 row partials are combined in LDS so a block issues one atomic per column.
-// grid = (ceil(N/512), ceil(M/rows_per_block))
-__global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ x, float* __restrict__ out, int M, int N,
-                                                     int ld, int rows_per_block) {
-  __shared__ float red[4][512];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int n0 = (blockIdx.x * 64 + tx) * 8;
-  const int r0 = blockIdx.y * rows_per_block;
-  const int r1 = min(M, r0 + rows_per_block);
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
-  if (n0 < N) {
-#pragma unroll 4
-    for (int r = r0 + ty; r < r1; r += 4) {
-      float f[8];
-      unpack8(*reinterpret_cast<const uint4*>(x + (size_t)r * ld + n0), f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += f[j];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[ty][tx * 8 + j] = acc[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < 512; c += 256) {
-    const int n = blockIdx.x * 512 + c;
-    if (n < N) atomicAdd(out + n, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
-  }
-}
-
-// same for wide rows (H > 1024: linear(2 * hidden -> T) behind the BiLSTM): the row is walked in 512-column chunks per tag
-// instead of being held in registers
-__global__ __launch_bounds__(256) void head_fwd_wide_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ bias, float* __restrict__ out, int R,
-                                                            int H, int T) {
-  const int lane = threadIdx.x % 64;
-  const int wave = blockIdx.x * 4 + threadIdx.x / 64;
-  const int nwave = gridDim.x * 4;
-  for (int r = wave; r < R; r += nwave) {
-    for (int t = 0; t < T; ++t) {
-      float acc = 0.0f;
-      for (int h0 = lane * 8; h0 < H; h0 += 512) {
-        float xv[8];
-        unpack8(*reinterpret_cast<const uint4*>(x + (size_t)r * H + h0), xv);
-        const float4 a = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0);
-        const float4 b = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0 + 4);
-        acc += xv[0] * a.x + xv[1] * a.y + xv[2] * a.z + xv[3] * a.w + xv[4] * b.x + xv[5] * b.y + xv[6] * b.z + xv[7] * b.w;
-      }
-      acc = wave_sum(acc);
-      if (lane == 0) out[(size_t)r * T + t] = acc + bias[t];
-    }
-  }
-}
-
-static inline int rows_grid(int R) {
-  int g = (R + 3) / 4;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  return g;
-}
-
 extern "C" {
-
-int kbner_gather_rows(const bf16_t* src, const int* idx, bf16_t* out, int R, int H, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, src, idx, out, R, H);
-  KBNER_LAUNCH_RET();
-}
-
-int kbner_scatter_rows(const bf16_t* dout, const int* idx, bf16_t* dsrc, int R, int H, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H);
-  KBNER_LAUNCH_RET();
-}
-
 int kbner_head_fwd(const bf16_t* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream) {
   KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= 8192 && T > 0 && T <= HEAD_MAXT);
   if (R == 0) return 0;
-  if (H <= 1024 && R <= 512)
+  if (H <= HEAD_MAXH && R <= 512)
     hipLaunchKernelGGL(head_fwd_rt_kernel, dim3((R * T + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, R, H, T);
-  else if (H <= 1024)
+  else if (H <= HEAD_MAXH)
     hipLaunchKernelGGL(head_fwd_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, R, H, T);
   else   // the BiLSTM tagger head of config 5: 2 x 1024 (padded) hidden columns
     hipLaunchKernelGGL(head_fwd_wide_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, R, H, T);
@@ -290,7 +332,7 @@ int kbner_head_fwd(const bf16_t* x, const float* w, const float* bias, float* ou
 }
 
 int kbner_head_bwd_dx(const float* de, const float* w, bf16_t* dx, int R, int H, int T, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= 1024 && T > 0 && T <= HEAD_MAXT);
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= HEAD_MAXH && T > 0 && T <= HEAD_MAXT);
   if (R == 0) return 0;
   hipLaunchKernelGGL(head_bwd_dx_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, de, w, dx, R, H, T);
   KBNER_LAUNCH_RET();
@@ -310,59 +352,39 @@ int kbner_head_bwd_dw(const float* de, const bf16_t* x, float* dw, float* db, in
                        dw, db, R, H, T);
   KBNER_LAUNCH_RET();
 }
-
-int kbner_colsum(const bf16_t* x, float* out, int M, int N, int ld, void* stream) {
-  KBNER_CHECK_ARG(M >= 0 && N > 0 && N % 8 == 0 && ld >= N && ld % 8 == 0);
-  if (M == 0) return 0;
-  int rpb = 128;
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 511) / 512, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, x, out,
-                     M, N, ld, rpb);
-  KBNER_LAUNCH_RET();
-}
-
 }  // extern "C"
 
-// fp32 row gather (evaluation path: compaction of the [B*n, T] emissions to the non-S-X rows before Viterbi / CRF loss):
-// out[r,:] = idx[r] >= 0 ? src[idx[r],:] : 0
-__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx,
-                                                              float* __restrict__ out, int R, int W) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= R * W) return;
-  const int r = i / W, c = i % W;
-  const int s = idx[r];
-  out[i] = s >= 0 ? src[(size_t)s * W + c] : 0.0f;
-}
+// ---- column sums
 
-extern "C" int kbner_gather_rows_f32(const float* src, const int* idx, float* out, int R, int W, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && W > 0);
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(gather_rows_f32_kernel, dim3((R * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, src, idx, out, R, W);
-  KBNER_LAUNCH_RET();
-}
-
-// Strided variant of gather_rows for the stacked-embedding concat of BASELINE config 5 (sequence_tagger_model.py:879-891:
-// torch.cat of every embedding's [B, n, D_i] features): embedding i's pooled rows are written straight into its column block
-// of the concatenated [rows, ld_out] matrix -- out[r, 0:H] = idx[r] >= 0 ? src[idx[r], 0:H] * mul : 0 -- so the concatenation
-// never exists as a separate copy.  16-byte accesses (H % 8 == 0, ld_out % 8 == 0, out 16-byte aligned).
-__global__ __launch_bounds__(256) void gather_rows_ld_kernel(const bf16_t* __restrict__ src, int ld_src, const int* __restrict__ idx,
-                                                             bf16_t* __restrict__ out, int ld_out, int R, int H8) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)R * H8) return;
-  const int r = (int)(i / H8), c = (int)(i % H8);
-  const int s = idx[r];
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (s >= 0) v = *reinterpret_cast<const uint4*>(src + (size_t)s * ld_src + c * 8);
-  *reinterpret_cast<uint4*>(out + (size_t)r * ld_out + c * 8) = v;
-}
-
-extern "C" int kbner_gather_rows_ld(const bf16_t* src, int ld_src, const int* idx, bf16_t* out, int ld_out, int R, int H,
-                                    void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0);
-  if (R == 0) return 0;
-  const size_t n = (size_t)R * (H / 8);
-  hipLaunchKernelGGL(gather_rows_ld_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, ld_src, idx,
-                     out, ld_out, R, H / 8);
-  KBNER_LAUNCH_RET();
+// out[n] += sum_m x[m,n]   (bf16 in, fp32 atomics out).  Block = 64 column-threads (16-byte loads, 512 columns)
+// x 4 row-threads; the 4 row partials are combined in LDS so a block issues one atomic per column.
+// grid = (ceil(N/512), ceil(M/rows_per_block))
+__global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ x, float* __restrict__ out, int M, int N,
+                                                     int ld, int rows_per_block) {
+  __shared__ float red[4][512];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int n0 = (blockIdx.x * 64 + tx) * 8;
+  const int r0 = blockIdx.y * rows_per_block;
+  const int r1 = min(M, r0 + rows_per_block);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
+  if (n0 < N) {
+#pragma unroll 4
+    for (int r = r0 + ty; r < r1; r += 4) {
+      float f[8];
+      unpack8bf(*reinterpret_cast<const uint4*>(x + (size_t)r * ld + n0), f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += f[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[ty][tx * 8 + j] = acc[j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < 512; c += 256) {
+    const int n = blockIdx.x * 512 + c;
+    if (n < N) atomicAdd(out + n, (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]));
+  }
 }
 
 // out[n] += sum_r ws[r, n]: folds the per-(tile row, wave row) column sums a GEMM launched with KBNER_EPI_COLSUM_WS left in
@@ -370,38 +392,31 @@ extern "C" int kbner_gather_rows_ld(const bf16_t* src, int ld_src, const int* id
 // fold `chunk` consecutive rows IN PLACE into the first row of their chunk (a block reads only its own chunk), then one row of
 // blocks folds those first rows into out.  (A single pass with 16 blocks ran at 150 GB/s: 55 us for 8 MB.)
 // block 256 columns x 4 row-lanes.
+// What the two fold kernels share: a block is 256 columns x 4 row-lanes (COLSUM_FOLD_BLOCK: tx, ty, column n); lane ty sums ELEM
+// (an expression in i and n) over the rows i = ty, ty + 4, ... < count into part[ty]; after the barrier COLSUM_FOLD_TOTAL is the
+// column's sum, for its owner (ty == 0 && n < N) to store.  Macros: as inline functions (the row pointer an argument), or with
+// the statements between them moved, the kernels' instruction streams change.
+#define COLSUM_FOLD_BLOCK                                  \
+  __shared__ float part[4][256];                           \
+  const int tx = threadIdx.x & 255, ty = threadIdx.x >> 8; \
+  const int n = blockIdx.x * 256 + tx
+#define COLSUM_FOLD_LANES(count, ELEM)                     \
+  float acc = 0.0f;                                        \
+  if (n < N)                                               \
+    for (int i = ty; i < count; i += 4) acc += ELEM;       \
+  part[ty][tx] = acc;                                      \
+  __syncthreads()
+#define COLSUM_FOLD_TOTAL ((part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]))
 __global__ __launch_bounds__(1024) void colsum_fold_kernel(float* __restrict__ ws, int first_stride, int stride, int count, int N,
                                                            float* __restrict__ out) {
-  __shared__ float part[4][256];
-  const int tx = threadIdx.x & 255, ty = threadIdx.x >> 8;
-  const int n = blockIdx.x * 256 + tx;
+  COLSUM_FOLD_BLOCK;
   float* base = ws + (size_t)blockIdx.y * first_stride * N;
-  float acc = 0.0f;
-  if (n < N)
-    for (int i = ty; i < count; i += 4) acc += base[(size_t)i * stride * N + n];
-  part[ty][tx] = acc;
-  __syncthreads();
+  COLSUM_FOLD_LANES(count, base[(size_t)i * stride * N + n]);
   if (ty == 0 && n < N) {
-    const float t = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
+    const float t = COLSUM_FOLD_TOTAL;
     if (out != nullptr) out[n] += t;
     else base[n] = t;
   }
-}
-
-extern "C" int kbner_colsum_rows_f32(float* ws, int rows, int N, float* out, void* stream) {
-  KBNER_CHECK_ARG(ws != nullptr && out != nullptr && rows > 0 && N > 0);
-  const int chunk = 16;
-  const dim3 gx((N + 255) / 256);
-  // (two passes only when there are enough partial rows to be worth a second launch: at 4 sentences per step the workspace has 32 rows
-  // and the second launch was half of this call's 9.6 us, 48 times per step)
-  if (rows > 4 * chunk && rows % chunk == 0) {
-    hipLaunchKernelGGL(colsum_fold_kernel, dim3(gx.x, rows / chunk), dim3(1024), 0, (hipStream_t)stream, ws, chunk, 1, chunk, N,
-                       (float*)nullptr);
-    hipLaunchKernelGGL(colsum_fold_kernel, gx, dim3(1024), 0, (hipStream_t)stream, ws, 0, chunk, rows / chunk, N, out);
-  } else {
-    hipLaunchKernelGGL(colsum_fold_kernel, gx, dim3(1024), 0, (hipStream_t)stream, ws, 0, 1, rows, N, out);
-  }
-  KBNER_LAUNCH_RET();
 }
 
 // The single-pass fold for up to COLSUM_BATCH_MAX workspaces of one width in ONE launch (blockIdx.y picks the item): the FFN-up bias
@@ -417,21 +432,41 @@ struct ColsumBatch {
   ColsumItem it[COLSUM_BATCH_MAX];
 };
 __global__ __launch_bounds__(1024) void colsum_fold_batched_kernel(const ColsumBatch batch, int N) {
-  __shared__ float part[4][256];
   const ColsumItem& q = batch.it[blockIdx.y];
-  const int tx = threadIdx.x & 255, ty = threadIdx.x >> 8;
-  const int n = blockIdx.x * 256 + tx;
+  COLSUM_FOLD_BLOCK;
   const int count = (int)q.rows;
-  float acc = 0.0f;
-  if (n < N)
-    for (int i = ty; i < count; i += 4) acc += q.ws[(size_t)i * N + n];
-  part[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && n < N) q.out[n] += (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
+  COLSUM_FOLD_LANES(count, q.ws[(size_t)i * N + n]);
+  if (ty == 0 && n < N) q.out[n] += COLSUM_FOLD_TOTAL;
+}
+
+extern "C" {
+int kbner_colsum(const bf16_t* x, float* out, int M, int N, int ld, void* stream) {
+  KBNER_CHECK_ARG(M >= 0 && N > 0 && N % 8 == 0 && ld >= N && ld % 8 == 0);
+  if (M == 0) return 0;
+  int rpb = 128;
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 511) / 512, (M + rpb - 1) / rpb), dim3(256), 0, (hipStream_t)stream, x, out,
+                     M, N, ld, rpb);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_colsum_rows_f32(float* ws, int rows, int N, float* out, void* stream) {
+  KBNER_CHECK_ARG(ws != nullptr && out != nullptr && rows > 0 && N > 0);
+  const int chunk = 16;
+  const dim3 gx((N + 255) / 256);
+  // (two passes only when there are enough partial rows to be worth a second launch: at 4 sentences per step the workspace has 32 rows
+  // and the second launch was half of this call's 9.6 us, 48 times per step)
+  if (rows > 4 * chunk && rows % chunk == 0) {
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3(gx.x, rows / chunk), dim3(1024), 0, (hipStream_t)stream, ws, chunk, 1, chunk, N,
+                       (float*)nullptr);
+    hipLaunchKernelGGL(colsum_fold_kernel, gx, dim3(1024), 0, (hipStream_t)stream, ws, 0, chunk, rows / chunk, N, out);
+  } else {
+    hipLaunchKernelGGL(colsum_fold_kernel, gx, dim3(1024), 0, (hipStream_t)stream, ws, 0, 1, rows, N, out);
+  }
+  KBNER_LAUNCH_RET();
 }
 
 // items (HOST memory, n <= 64 records of 3 x 64 bits: ws, out -- device pointers -- and the number of rows): out[c] += sum_r ws[r, c]
-extern "C" int kbner_colsum_rows_f32_batched(const long long* items, int n, int N, void* stream) {
+int kbner_colsum_rows_f32_batched(const long long* items, int n, int N, void* stream) {
   KBNER_CHECK_ARG(items != nullptr && n >= 0 && n <= COLSUM_BATCH_MAX && N > 0);
   if (n == 0) return 0;
   ColsumBatch b;
@@ -445,49 +480,32 @@ extern "C" int kbner_colsum_rows_f32_batched(const long long* items, int n, int 
   hipLaunchKernelGGL(colsum_fold_batched_kernel, dim3((N + 255) / 256, n), dim3(1024), 0, (hipStream_t)stream, b, N);
   KBNER_LAUNCH_RET();
 }
+}  // extern "C"
 
-// fp32 row scatter (data-parallel exchange of the touched word-embedding gradient rows, kbner/dp.py): dst[idx[r],:] = rows[r,:];
-// indices unique, 16-byte accesses (W % 4 == 0)
-__global__ __launch_bounds__(256) void scatter_rows_f32_kernel(const float4* __restrict__ rows, const int* __restrict__ idx,
-                                                               float4* __restrict__ dst, int R, int W4) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)R * W4) return;
-  const int r = (int)(i / W4), c = (int)(i % W4);
-  const int d = idx[r];
-  if (d >= 0) dst[(size_t)d * W4 + c] = rows[i];
+// ---- split-K finish
+
+// Split-K finish: C[m,n] = bf16( dropout( sum_s ws[s][m][n] + bias[n] ) + addend[m,n] ).  The forward / dgrad GEMMs of a small
+// micro-batch have a few dozen 256x256 tiles, each a serial chain of K/64 DMA round trips; splitting a long K over up to 4
+// workgroups (fp32 slabs written with plain stores by KBNER_EPI_STORE32) shortens that chain, this pass folds the slabs.
+__global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ ws, int splits, size_t slab, const float* __restrict__ bias,
+                                                            const bf16_t* __restrict__ addend, int ldadd, bf16_t* __restrict__ C, int ldc, int M,
+                                                            int N, uint32_t drop_seed, uint32_t drop_thresh) {
+  const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;  // 8 consecutive columns per thread
+  if (i >= (size_t)M * N) return;
+  const int m = (int)(i / N), n = (int)(i % N);
+  *reinterpret_cast<uint4*>(C + (size_t)m * ldc + n) = splitk_fold8_pack(ws, splits, slab, bias, addend, ldadd, m, n, N, drop_seed, drop_thresh);
 }
 
-extern "C" int kbner_scatter_rows_f32(const float* rows, const int* idx, float* dst, int R, int W, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && W > 0 && W % 4 == 0);
-  if (R == 0) return 0;
-  const size_t n = (size_t)R * (W / 4);
-  hipLaunchKernelGGL(scatter_rows_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const float4*>(rows), idx, reinterpret_cast<float4*>(dst), R, W / 4);
+extern "C" int kbner_splitk_finish(const float* ws, int splits, const float* bias, const bf16_t* addend, int ldadd, bf16_t* C, int ldc,
+                                   int M, int N, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
+  KBNER_CHECK_ARG(ws != nullptr && C != nullptr && splits >= 1 && splits <= 8 && M > 0 && N > 0 && N % 8 == 0 && ldc % 8 == 0);
+  KBNER_CHECK_ARG(addend == nullptr || ldadd % 8 == 0);
+  FLAT_LAUNCH(splitk_finish_kernel, (size_t)M * N / 8, stream, ws, splits, (size_t)M * N, bias, addend, ldadd, C, ldc, M, N, drop_seed,
+              drop_thresh);
   KBNER_LAUNCH_RET();
 }
 
-// fp32 row scatter-ADD, any width: dst[idx[r],:] += rows[r,:] for idx[r] >= 0 (indices unique: plain read-modify-write).
-// The knowledge-distillation step (kbner/engine.py:Tagger.kd_loss) folds the gradient of the gold-label NLL, computed on the
-// rows left after the remove_x compaction, back into the gradient of the all-token emissions the KD terms are defined on
-// (the backward of the masked_select compaction, sequence_tagger_model.py:2474-2488, under autograd in the reference).
-__global__ __launch_bounds__(256) void scatter_add_rows_f32_kernel(const float* __restrict__ rows, const int* __restrict__ idx,
-                                                                   float* __restrict__ dst, int R, int W) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)R * W) return;
-  const int r = (int)(i / W), c = (int)(i % W);
-  const int d = idx[r];
-  if (d >= 0) dst[(size_t)d * W + c] += rows[i];
-}
-
-extern "C" int kbner_scatter_add_rows_f32(const float* rows, const int* idx, float* dst, int R, int W, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && W > 0);
-  if (R == 0) return 0;
-  KBNER_CHECK_ARG(rows != nullptr && idx != nullptr && dst != nullptr);
-  const size_t n = (size_t)R * W;
-  hipLaunchKernelGGL(scatter_add_rows_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, idx,
-                     dst, R, W);
-  KBNER_LAUNCH_RET();
-}
+// ---- the rest
 
 // Multi-view training's representation term (FastSequenceTagger._calculate_multi_view_loss with calculate_l2_loss,
 // sequence_tagger_model.py:1988-1996,2026-2035): mse_loss(orig view's token representations, the context view's (detached)) at the
@@ -521,16 +539,6 @@ __global__ __launch_bounds__(256) void l2_rows_kernel(const bf16_t* __restrict__
   if (lane == 0) atomicAdd(loss, wr * acc);
 }
 
-extern "C" int kbner_l2_rows(const bf16_t* a, const bf16_t* b, const float* w, float gscale, bf16_t* da, float* loss, int R, int H,
-                             void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 2 == 0);
-  if (R == 0) return 0;
-  KBNER_CHECK_ARG(a != nullptr && b != nullptr && w != nullptr && loss != nullptr);
-  hipLaunchKernelGGL(l2_rows_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, w, gscale, da, loss, R,
-                     H);
-  KBNER_LAUNCH_RET();
-}
-
 // Materialise a dropout site's multiplier (tests / debugging only: the product kernels regenerate it in registers):
 // out[z,i,j] = drop_keep(rowkey(seed, z*M+i), colkey(seed, z*N+j)) ? 1/(1-p) : 0.  Hidden-state sites: Z=1, [M tokens, H];
 // attention-probability sites: Z = B*A heads, M = N = S.
@@ -545,33 +553,20 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(float* __restrict__ o
   out[i] = keep ? drop_scale(thresh) : 0.0f;
 }
 
-extern "C" int kbner_dropout_mask(float* out, int Z, int M, int N, uint32_t seed, uint32_t thresh, void* stream) {
+extern "C" {
+int kbner_l2_rows(const bf16_t* a, const bf16_t* b, const float* w, float gscale, bf16_t* da, float* loss, int R, int H,
+                             void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 2 == 0);
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(a != nullptr && b != nullptr && w != nullptr && loss != nullptr);
+  hipLaunchKernelGGL(l2_rows_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, w, gscale, da, loss, R,
+                     H);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_dropout_mask(float* out, int Z, int M, int N, uint32_t seed, uint32_t thresh, void* stream) {
   KBNER_CHECK_ARG(out != nullptr && Z > 0 && M > 0 && N > 0);
-  const size_t n = (size_t)Z * M * N;
-  hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, Z, M, N, seed,
-                     thresh);
+  FLAT_LAUNCH(dropout_mask_kernel, (size_t)Z * M * N, stream, out, Z, M, N, seed, thresh);
   KBNER_LAUNCH_RET();
 }
-
-
-// Split-K finish: C[m,n] = bf16( dropout( sum_s ws[s][m][n] + bias[n] ) + addend[m,n] ).  The forward / dgrad GEMMs of a small
-// micro-batch have a few dozen 256x256 tiles, each a serial chain of K/64 DMA round trips; splitting a long K over up to 4
-// workgroups (fp32 slabs written with plain stores by KBNER_EPI_STORE32) shortens that chain, this pass folds the slabs.
-__global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ ws, int splits, size_t slab, const float* __restrict__ bias,
-                                                            const bf16_t* __restrict__ addend, int ldadd, bf16_t* __restrict__ C, int ldc, int M,
-                                                            int N, uint32_t drop_seed, uint32_t drop_thresh) {
-  const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;  // 8 consecutive columns per thread
-  if (i >= (size_t)M * N) return;
-  const int m = (int)(i / N), n = (int)(i % N);
-  *reinterpret_cast<uint4*>(C + (size_t)m * ldc + n) = splitk_fold8_pack(ws, splits, slab, bias, addend, ldadd, m, n, N, drop_seed, drop_thresh);
-}
-
-extern "C" int kbner_splitk_finish(const float* ws, int splits, const float* bias, const bf16_t* addend, int ldadd, bf16_t* C, int ldc,
-                                   int M, int N, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
-  KBNER_CHECK_ARG(ws != nullptr && C != nullptr && splits >= 1 && splits <= 8 && M > 0 && N > 0 && N % 8 == 0 && ldc % 8 == 0);
-  KBNER_CHECK_ARG(addend == nullptr || ldadd % 8 == 0);
-  const size_t n8 = (size_t)M * N / 8;
-  hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, splits, (size_t)M * N,
-                     bias, addend, ldadd, C, ldc, M, N, drop_seed, drop_thresh);
-  KBNER_LAUNCH_RET();
-}
+}  // extern "C"
