@@ -192,9 +192,14 @@ def test_layernorm(st, M, H):
     assert r["dgamma"] < 2e-3 and r["dbeta"] < 2e-3 and r["dbias"] < 2e-2, r
 
 
-@pytest.mark.parametrize("B,n", [(3, 7), (32, 64), (256, 32), (32, 16), (8, 512), (32, 512), (1, 1)])   # incl. the four (B, n) points of BASELINE cfg 5
-def test_crf_vs_oracle(st, B, n):
-    r = st.check_crf(B, n)
+CRF_ORACLE_CASES = [(3, 7), (32, 64), (256, 32), (32, 16), (8, 512), (32, 512), (1, 1)]   # incl. the four (B, n) points of BASELINE cfg 5
+CRF_ORACLE_WIDE = [(8, 40, 33, 0, 32), (8, 40, 64, 17, 5)]   # the 64-wide kernels, START / STOP away from the last two ids
+
+
+@pytest.mark.parametrize("B,n,T,start,stop", [pytest.param(B, n, 29, 27, 28, id="%d-%d" % (B, n)) for B, n in CRF_ORACLE_CASES]
+                         + [pytest.param(*c, id="-".join(map(str, c))) for c in CRF_ORACLE_WIDE])
+def test_crf_vs_oracle(st, B, n, T, start, stop):
+    r = st.check_crf(B, n, T, start, stop)
     assert r["tags_equal"] and r["popped_ok"], r       # Viterbi: bit-exact tag indices
     assert r["conf"] < 2e-6 and r["logz"] < 2e-6 and r["gold"] < 2e-6, r
     # marginals come from exp(alpha + beta - logZ) with |alpha| ~ O(n): fp32 absolute error grows ~ n * 2^-23 * |score|
