@@ -140,6 +140,18 @@ int kbner_l2_rows(const kbner_bf16* a, const kbner_bf16* b, const float* w, floa
                   void* stream);
 /* its backward (unique indices; caller zero-fills dsrc) */
 int kbner_scatter_rows(const kbner_bf16* dout, const int* idx, kbner_bf16* dsrc, int R, int H, void* stream);
+/* kbner_gather_rows / kbner_scatter_rows with the tagger head's dropout on the token features (sequence_tagger_model.py:959-964:
+ * torch.nn.Dropout, then flair's LockedDropout, flair/nn.py:142-159) applied on the way through.  Rows are laid out [B, n]
+ * (R = B * n, R % n == 0), so row r belongs to sentence r / n.  With the keep test and scale of the dropout section below:
+ *   m_e(r,h) = element (r, h)     of site (seed_e, thresh_e)   -- one mask value per element
+ *   m_l(r,h) = element (r / n, h) of site (seed_l, thresh_l)   -- one per (sentence, column), shared by the sentence's n rows
+ *   gather : out[r,h]       = idx[r] >= 0 ? bf16(src[idx[r],h] * (m_e * m_l)) : 0       (m_e * m_l formed in fp32, one rounding)
+ *   scatter: dsrc[idx[r],h] = bf16(dout[r,h] * (m_e * m_l))   for idx[r] >= 0           (unique indices; caller zero-fills dsrc)
+ * A threshold of 0 disables its site; with both 0 these are kbner_gather_rows / kbner_scatter_rows, byte for byte. */
+int kbner_gather_rows_drop(const kbner_bf16* src, const int* idx, kbner_bf16* out, int R, int H, int n, uint32_t seed_e,
+                           uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+int kbner_scatter_rows_drop(const kbner_bf16* dout, const int* idx, kbner_bf16* dsrc, int R, int H, int n, uint32_t seed_e,
+                            uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 /* self.linear, sequence_tagger_model.py:1027: out f32[R,T] = x bf16[R,H] . w f32[T,H]^T + bias */
 int kbner_head_fwd(const kbner_bf16* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream);
 int kbner_head_bwd_dx(const float* de, const float* w, kbner_bf16* dx, int R, int H, int T, void* stream);
@@ -193,6 +205,9 @@ int kbner_embed_ln_bwd_mark(const kbner_bf16* dy, const kbner_bf16* h0, const fl
  * Counter-based and replayable: element (i,j) of a site is kept iff
  *   mul24(mix(seed + i) ^ mix((seed*0x9E3779B1 + 0x7F4A7C15) ^ j), 0x9E3779) >= drop_thresh,  drop_thresh = p * 2^32 (mul24: the low 24 bits of both factors, low 32 bits of the product),
  * kept values are scaled by 1/(1-p).  No mask is stored: backward passes the same (seed, thresh).  drop_thresh = 0 disables.
+ * The tagger head's two sites (kbner_gather_rows_drop / kbner_scatter_rows_drop) key the [B*n, H] token features as
+ *   head dropout   (i, j) = (row r, column h)            locked dropout   (i, j) = (sentence r / n, column h)
+ * each with a seed of its own.
  * kbner_dropout_mask materialises the multiplier (tests): out f32[Z,M,N], element (z,i,j) -> keys (z*M+i, z*N+j). */
 int kbner_dropout_mask(float* out, int Z, int M, int N, uint32_t seed, uint32_t thresh, void* stream);
 

@@ -53,6 +53,47 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16_t* __restr
   }
 }
 
+// gather_rows / scatter_rows with the tagger head's two dropout sites on the token features (sequence_tagger_model.py:959-964):
+// torch.nn.Dropout -- element (row r, column h) of site e -- and flair's LockedDropout (flair/nn.py:142-159) -- ONE mask per
+// (sentence, column), shared by the n rows of a sentence: element (r / n, h) of site l; rows are laid out [B, n].
+//     gather : out[r,:]       = idx[r] >= 0 ? bf16(src[idx[r],:] * m[r,:]) : 0
+//     scatter: dsrc[idx[r],:] = bf16(dout[r,:] * m[r,:])   for idx[r] >= 0                m = m_e * m_l, formed in fp32
+// (m_x = kept ? 1/(1-p_x) : 0; thresh 0: every element kept, scale 1).  Same shape as the plain pair: one wave per row, 16-byte
+// accesses; the column keys of both sites depend on h alone, so the 512-column chunk is the OUTER loop and they stay in
+// registers over the rows.  The row keys are wave-uniform (scalar registers).  SCATTER: idx addresses the output rows.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void rows_drop_kernel(const bf16_t* __restrict__ in, const int* __restrict__ idx,
+                                                        bf16_t* __restrict__ out, int R, int H, int n, uint32_t seed_e,
+                                                        uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l) {
+  const int lane = threadIdx.x % 64;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + threadIdx.x / 64);
+  const int nwave = gridDim.x * 4;
+  const float scale = drop_scale(thresh_e) * drop_scale(thresh_l);
+  for (int h0 = lane * 8; h0 < H; h0 += 512) {
+    uint32_t cke[8], ckl[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      cke[j] = drop_colkey(seed_e, (uint32_t)(h0 + j));
+      ckl[j] = drop_colkey(seed_l, (uint32_t)(h0 + j));
+    }
+    for (int r = wave; r < R; r += nwave) {
+      const int s = idx[r];
+      if (s < 0) {
+        if (!SCATTER) *reinterpret_cast<uint4*>(out + (size_t)r * H + h0) = make_uint4(0, 0, 0, 0);
+        continue;
+      }
+      const uint32_t rke = drop_rowkey(seed_e, (uint32_t)r);
+      const uint32_t rkl = drop_rowkey(seed_l, (uint32_t)(r / n));
+      float v[8];
+      unpack8bf(*reinterpret_cast<const uint4*>(in + (size_t)(SCATTER ? r : s) * H + h0), v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] *= (drop_keep(rke, cke[j], thresh_e) && drop_keep(rkl, ckl[j], thresh_l)) ? scale : 0.0f;
+      *reinterpret_cast<uint4*>(out + (size_t)(SCATTER ? s : r) * H + h0) = pack8bf(v);
+    }
+  }
+}
+
 // fp32 row gather (evaluation path: compaction of the [B*n, T] emissions to the non-S-X rows before Viterbi / CRF loss):
 // out[r,:] = idx[r] >= 0 ? src[idx[r],:] : 0
 __global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx,
@@ -115,6 +156,31 @@ int kbner_scatter_rows(const bf16_t* dout, const int* idx, bf16_t* dsrc, int R, 
   KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
   if (R == 0) return 0;
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H);
+  KBNER_LAUNCH_RET();
+}
+
+// both thresholds 0: the plain kernels (the same bytes, no multiply)
+int kbner_gather_rows_drop(const bf16_t* src, const int* idx, bf16_t* out, int R, int H, int n, uint32_t seed_e, uint32_t thresh_e,
+                           uint32_t seed_l, uint32_t thresh_l, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && n >= 1 && R % n == 0);
+  if (R == 0) return 0;
+  if (thresh_e == 0 && thresh_l == 0)
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, src, idx, out, R, H);
+  else
+    hipLaunchKernelGGL(rows_drop_kernel<false>, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, src, idx, out, R, H, n, seed_e,
+                       thresh_e, seed_l, thresh_l);
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_scatter_rows_drop(const bf16_t* dout, const int* idx, bf16_t* dsrc, int R, int H, int n, uint32_t seed_e, uint32_t thresh_e,
+                            uint32_t seed_l, uint32_t thresh_l, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && n >= 1 && R % n == 0);
+  if (R == 0) return 0;
+  if (thresh_e == 0 && thresh_l == 0)
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H);
+  else
+    hipLaunchKernelGGL(rows_drop_kernel<true>, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H, n, seed_e,
+                       thresh_e, seed_l, thresh_l);
   KBNER_LAUNCH_RET();
 }
 

@@ -167,8 +167,12 @@ class SequenceTagger(flair.nn.Model):
             if hasattr(embeddings, "embeddings") and len(embeddings.embeddings) != 1:
                 raise NotImplementedError("the fine-tuning path (use_rnn: false) takes exactly one TransformerWordEmbeddings; "
                                           "stacked embeddings go with use_rnn: true (inference)")
-            if dropout or locked_dropout:
-                raise NotImplementedError("dropout / locked_dropout > 0 on the tagger head is not implemented (KB-NER YAMLs use 0.0)")
+            for k, p in (("dropout", dropout), ("locked_dropout", locked_dropout)):
+                if not 0.0 <= float(p or 0.0) < 1.0:
+                    raise ValueError("%s must be in [0, 1) (got %r)" % (k, p))
+            # torch.nn.Dropout and flair.nn.LockedDropout on the token features while training (sequence_tagger_model.py:959-964;
+            # engine.head_dropout / engine.locked_dropout, applied by the kept-token gather)
+            self.use_dropout, self.use_locked_dropout = float(dropout or 0.0), float(locked_dropout or 0.0)
             self._build_engine()
 
     # ------------------------------------------------------------------ engine
@@ -187,6 +191,7 @@ class SequenceTagger(flair.nn.Model):
         # dropout streams differ per data-parallel rank (each rank sees different sentences anyway)
         self.engine.seed_dropout(int(torch.initial_seed() % (2 ** 31)) + 7919 * int(os.environ.get("RANK", "0")))
         self.engine.word_dropout = float(self.use_word_dropout or 0.0)
+        self.engine.head_dropout, self.engine.locked_dropout = self.use_dropout, self.use_locked_dropout
         self.engine.load_hf_state_dict(self._emb.model.state_dict())
         g = torch.Generator().manual_seed(int(torch.initial_seed() % (2 ** 31)))
         H = cfg.hidden_size
@@ -974,7 +979,8 @@ class SequenceTagger(flair.nn.Model):
             "transitions": self.engine.arena.param("transitions").detach().cpu().clone(),
             "tag_dictionary": self.tag_dictionary, "tag_type": self.tag_type, "hidden_size": self.hidden_size,
             "use_crf": self.use_crf, "use_rnn": False, "remove_x": self.remove_x, "sentence_loss": self.sentence_level_loss,
-            "word_dropout": self.use_word_dropout, "embedding_model_dir": getattr(self._emb, "name", None),
+            "word_dropout": self.use_word_dropout, "dropout": self.use_dropout, "locked_dropout": self.use_locked_dropout,
+            "embedding_model_dir": getattr(self._emb, "name", None),
             "trained_epochs": self.trained_epochs,
             # loss switches, so that a model re-loaded as a student (load_pretrained) keeps training the way it was configured
             "temperature": self.temperature, "multi_view_training": self.multi_view_training,
@@ -989,8 +995,8 @@ class SequenceTagger(flair.nn.Model):
         emb = TransformerWordEmbeddings(model=state["embedding_model_dir"], layers="-1", pooling_operation="first", fine_tune=True)
         model = cls(hidden_size=state["hidden_size"], embeddings=StackedEmbeddings([emb]), tag_dictionary=state["tag_dictionary"],
                     tag_type=state["tag_type"], use_crf=bool(state.get("use_crf", True)), use_rnn=False, remove_x=state["remove_x"],
-                    sentence_loss=state["sentence_loss"], word_dropout=state.get("word_dropout", 0.0), dropout=0.0,
-                    locked_dropout=0.0, temperature=state.get("temperature", 1),
+                    sentence_loss=state["sentence_loss"], word_dropout=state.get("word_dropout", 0.0),
+                    dropout=state.get("dropout", 0.0), locked_dropout=state.get("locked_dropout", 0.0), temperature=state.get("temperature", 1),
                     **{k: state.get(k, False) for k in ("multi_view_training", "distill_posterior", "distill_crf", "distill_exact",
                                                         "crf_attention", "distill_with_gold", "exp_score", "calculate_l2_loss", "l2_loss_only")},
                     gold_const=state.get("gold_const", 1.0))

@@ -302,6 +302,10 @@ class Tagger:
         # zeroed across the batch, no rescale).  Masks are counter-based (include/kbner.h): only seeds are stored.
         self.training = False
         self.word_dropout = 0.0
+        # the reference's other two sites on the token features (sequence_tagger_model.py:959-964): torch.nn.Dropout (element-wise)
+        # and flair's LockedDropout (flair/nn.py:142-159: one mask per (sentence, feature), shared by the sentence's tokens)
+        self.head_dropout = 0.0
+        self.locked_dropout = 0.0
         self.seed_dropout(20220711)
         # data-parallel runs: the persistent GEMM draws its tiles dynamically (kbner_gemm_bf16_grouped_dyn) so that CUs taken
         # by an overlapped RCCL collective cost their share of the launch, not a second pass; off for a single process.
@@ -661,10 +665,26 @@ class Tagger:
                          splitk=_splitk((n_ // 128) * (k_ // 128), Mp))
 
     # ---------------------------------------------------------------- tagger head
-    def emissions(self, hidden, row_idx, B, n):
+    def _head_drop(self):
+        """per training forward with head / locked dropout on: ((seed, thresh) of the element mask, (seed, thresh) of the locked
+        mask), else None.  ONE draw of two seeds from the engine's stream, after the forward's word-dropout draw; nothing is drawn
+        with both rates 0.  The pair travels with the forward's results to ITS backward (multi-view and KD steps run several
+        forwards before the first backward)."""
+        if not (self.training and (self.head_dropout > 0.0 or self.locked_dropout > 0.0)):
+            return None
+        sd = self._drop_rng.integers(0, 2 ** 32, size=2, dtype="uint64")
+        return (int(sd[0]), ops.drop_thresh(self.head_dropout)), (int(sd[1]), ops.drop_thresh(self.locked_dropout))
+
+    def emissions(self, hidden, row_idx, B, n, drop=None):
         """gather rows (first sub-token of each word token, -1 -> zeros) then the linear head.
-        -> (features f32 [B,n,T], pooled bf16 [B*n,H])"""
-        pooled = ops.gather_rows(hidden, row_idx)
+        -> (features f32 [B,n,T], pooled bf16 [B*n,H]).  drop (from _head_drop): the gather applies the head's element and locked
+        dropout in the reference's order -- element mask, word dropout (the -1 rows), locked mask -- and `pooled` is what the head
+        read.  Under remove_x the reference masks all tokens and compacts afterwards; here the compacted rows are masked (row key =
+        compacted row, sentence key = row // n): independent Bernoulli draws either way, the same distribution."""
+        if drop is None:
+            pooled = ops.gather_rows(hidden, row_idx)
+        else:
+            pooled = ops.gather_rows_drop(hidden, row_idx, n, drop[0], drop[1])
         em = ops.head_fwd(pooled, self.arena.param("linear.weight"), self.arena.param("linear.bias"))
         return em.view(B, n, self.T), pooled
 
@@ -693,7 +713,8 @@ class Tagger:
                 ops.sched_ring_reset(None)
 
     def _emit(self, batch):
-        """encoder -> (WordDropout) kept-token gather -> head: (em f32[B,nc,T], pooled bf16[B*nc,H], crow_idx, B, nc, R, S)"""
+        """encoder -> (WordDropout) kept-token gather (+ head / locked dropout) -> head:
+        (em f32[B,nc,T], pooled bf16[B*nc,H], crow_idx, B, nc, R, S, drop); drop = this forward's _head_drop(), for its backward"""
         B, S = batch["B"], batch["S"]
         R = batch.get("R", B)  # encoder rows (> B when long sentences were split into sliding windows)
         hidden = self.encoder_forward(batch["ids"], batch["pos_ids"], batch["maskbias"], R, S)
@@ -707,11 +728,14 @@ class Tagger:
             dropped = torch.from_numpy(self._last_word_dropped).to(self.device)
             cpos = batch["cpos"].long()
             crow_idx = torch.where(dropped[cpos.clamp(min=0)] & (cpos >= 0), torch.full_like(crow_idx, -1), crow_idx)
-        em, pooled = self.emissions(hidden, crow_idx, B, nc)
-        return em, pooled, crow_idx, B, nc, R, S
+        drop = self._head_drop()
+        em, pooled = self.emissions(hidden, crow_idx, B, nc, drop)
+        return em, pooled, crow_idx, B, nc, R, S, drop
 
-    def _backprop_emissions(self, demit, pooled, crow_idx, B, nc, R, S, grad_ready, l2=None, l2_scale=1.0):
+    def _backprop_emissions(self, demit, pooled, crow_idx, B, nc, R, S, grad_ready, l2=None, l2_scale=1.0, drop=None):
         """d loss / d emissions f32[B,nc,T] -> head, scatter to the encoder rows, encoder backward (all into arena.g).
+        drop: what _emit returned for the forward that produced `pooled` -- the scatter replays that forward's masks (the l2 term
+        below is a function of the masked rows, so its gradient passes through the masks too: the chain rule).
         l2 = (other view's pooled rows bf16[B*nc,H], row weights f32[B*nc]): the representation term of multi-view training is
         added to the pooled-row gradient here; its value is returned (0-d tensor), else None."""
         a = self.arena
@@ -724,7 +748,10 @@ class Tagger:
             l2_val = part[0]
         ac = self.acts(R, S)
         ac.dx.zero_()
-        ops.scatter_rows(dpooled, crow_idx, ac.dx)
+        if drop is None:
+            ops.scatter_rows(dpooled, crow_idx, ac.dx)
+        else:
+            ops.scatter_rows_drop(dpooled, crow_idx, ac.dx, nc, drop[0], drop[1])
         self.encoder_backward(ac.dx, grad_ready)
         return l2_val
 
@@ -741,7 +768,7 @@ class Tagger:
         return w
 
     def _forward_loss(self, batch, loss_scale, backward, weights, grad_ready=None):
-        em, pooled, crow_idx, B, nc, R, S = self._emit(batch)
+        em, pooled, crow_idx, B, nc, R, S, drop = self._emit(batch)
         self.last_emissions = em   # f32 [B, nc, T] at the kept (non-S-X) tokens: the teacher view of multi-view training
         self.last_pooled = pooled.view(B, nc, -1)   # bf16 [B, nc, H]: the same view's token representations (calculate_l2_loss)
         a = self.arena
@@ -754,7 +781,7 @@ class Tagger:
             per, demit = ops.softmax_ce(em, batch["ctags"], batch["clens"], w * loss_scale)
             ops.wdiff_sum(per, torch.zeros_like(per), w, loss)
             if backward:
-                self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready)
+                self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready, drop=drop)
             return loss[0]
         logz, gold, alpha = ops.crf_nll_fwd(em, trans, batch["ctags"], batch["clens"], self.start, self.stop)
         ops.wdiff_sum(logz, gold, w, loss)
@@ -770,7 +797,7 @@ class Tagger:
                 dl = w * loss_scale
             demit = ops.crf_nll_bwd(em, trans, batch["ctags"], batch["clens"], alpha, logz, dl, self.start, self.stop,
                                     a.grad("transitions"))
-            self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready)
+            self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready, drop=drop)
         return loss[0]
 
     def distill_loss(self, batch, teacher_emissions, tau, loss_scale=1.0, backward=True, weights=None, grad_ready=None,
@@ -807,7 +834,7 @@ class Tagger:
         return (per * w).sum(), demit
 
     def _distill_loss(self, batch, te, tau, loss_scale, backward, weights, grad_ready, mode="posterior", tp=None, l2_only=False):
-        em, pooled, crow_idx, B, nc, R, S = self._emit(batch)
+        em, pooled, crow_idx, B, nc, R, S, drop = self._emit(batch)
         if te.shape[0] != B or te.shape[2] != self.T:
             raise ValueError("teacher emissions must be [B, n, T] for the same B sentences")
         if te.shape[1] < nc:   # (a real-token count mismatch between the views is a data error; the kernel only reads < lens)
@@ -833,7 +860,7 @@ class Tagger:
                 ops.l2_rows(pooled, l2[0], wrow, part)
                 loss = loss + part[0]
         if backward:
-            part = self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready, l2=l2, l2_scale=loss_scale)
+            part = self._backprop_emissions(demit, pooled, crow_idx, B, nc, R, S, grad_ready, l2=l2, l2_scale=loss_scale, drop=drop)
             if part is not None:
                 loss = loss + part
         return loss
@@ -866,11 +893,12 @@ class Tagger:
             self._last_word_dropped = self._drop_rng.random(n) < self.word_dropout
             dropped = torch.from_numpy(self._last_word_dropped).to(self.device).repeat(B)
             row_idx = torch.where(dropped, torch.full_like(row_idx, -1), row_idx)
-        em, pooled = self.emissions(hidden, row_idx, B, n)
+        drop = self._head_drop()
+        em, pooled = self.emissions(hidden, row_idx, B, n, drop)
         self.last_emissions = em
         loss, demit = self.kd_crf_terms(em, batch, kd, interpolation, tau, loss_scale, backward, weights)
         if backward:
-            self._backprop_emissions(demit, pooled, row_idx, B, n, R, S, grad_ready)
+            self._backprop_emissions(demit, pooled, row_idx, B, n, R, S, grad_ready, drop=drop)
         return loss
 
     def kd_crf_terms(self, em, batch, kd, interpolation, tau, loss_scale=1.0, backward=True, weights=None, dtrans=None):

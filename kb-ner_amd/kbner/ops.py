@@ -271,6 +271,38 @@ def scatter_rows(dout, idx, dsrc):
     L.call("kbner_scatter_rows", ptr(dout), ptr(idx), ptr(dsrc), idx.numel(), dout.shape[-1], stream_ptr())
 
 
+def _drop_rows_args(name, rows, idx, other, n, drop_e, drop_l):
+    R, H = idx.numel(), rows.shape[-1]
+    if rows.dim() != 2 or other.dim() != 2 or other.shape[-1] != H or H % 8 or n < 1 or R % n:
+        raise L.KbnerError("%s: bf16 [*, H] rows with H %% 8 == 0, idx [B * n] with n >= 1" % name)
+    (se, te), (sl, tl) = drop_e, drop_l
+    return R, H, int(n), int(se) & 0xFFFFFFFF, int(te), int(sl) & 0xFFFFFFFF, int(tl)
+
+
+def gather_rows_drop(src, idx, n, drop_e=NO_DROP, drop_l=NO_DROP, out=None):
+    """gather_rows with the tagger head's dropout applied: out[r] = src[idx[r]] * m_e[r] * m_l[r // n] (-1 -> zeros); rows are
+    [B, n], drop_e = (seed, thresh) of the element mask, drop_l of the per-(sentence, column) locked mask (include/kbner.h)"""
+    _chk(src, BF16, "src"); _chk(idx, I32, "idx")
+    if out is None:
+        out = torch.empty((idx.numel(), src.shape[-1]), dtype=BF16, device=src.device)
+    else:
+        _chk(out, BF16, "out")
+    R, H, n, se, te, sl, tl = _drop_rows_args("gather_rows_drop", src, idx, out, n, drop_e, drop_l)
+    if out.shape[0] < R:
+        raise L.KbnerError("gather_rows_drop: out holds fewer rows than idx names")
+    L.call("kbner_gather_rows_drop", ptr(src), ptr(idx), ptr(out), R, H, n, se, te, sl, tl, stream_ptr())
+    return out
+
+
+def scatter_rows_drop(dout, idx, dsrc, n, drop_e=NO_DROP, drop_l=NO_DROP):
+    """its backward: dsrc[idx[r]] = dout[r] * m_e[r] * m_l[r // n] for idx[r] >= 0 (unique indices; the caller zero-fills dsrc)"""
+    _chk(dout, BF16, "dout"); _chk(idx, I32, "idx"); _chk(dsrc, BF16, "dsrc")
+    R, H, n, se, te, sl, tl = _drop_rows_args("scatter_rows_drop", dout, idx, dsrc, n, drop_e, drop_l)
+    if dout.shape[0] < R:
+        raise L.KbnerError("scatter_rows_drop: dout holds fewer rows than idx names")
+    L.call("kbner_scatter_rows_drop", ptr(dout), ptr(idx), ptr(dsrc), R, H, n, se, te, sl, tl, stream_ptr())
+
+
 def head_fwd(x, w, bias):
     _chk(x, BF16, "x"); _chk(w, F32, "w"); _chk(bias, F32, "bias")
     R, H = x.shape
