@@ -55,6 +55,32 @@ int kbner_crf_nll_bwd(const float* emit, const float* trans, const int* tags, co
 int kbner_crf_posterior(const float* emit, const float* trans, const int* lens, const float* alpha, const float* logz, int B,
                         int n, int T, int start, int stop, float* marg, void* stream);
 
+/* ---- tag sets of 65 to 192 tags: the same four operations, one WORKGROUP per sentence (csrc/crf_wide.hip) ----
+ * The functions above put one tag on one lane of a single wave and stop at 64 tags; these take every 1 <= T <= KBNER_CRF_WIDE_MAXT
+ * with the same argument types, layouts and results (trans[to,from], START / STOP anywhere in [0,T), alpha f32[B,n+1,T] with row 0
+ * = 0 at START and -1e12 elsewhere, dtrans ADDED to, tags = -1 and conf = 0 past lens[b], demit / marg zero past lens[b], popped
+ * nullable, B == 0 returns 0), so either family can be checked against the other where both apply.  192 is where the backward
+ * kernel's LDS-resident transition matrix (fp32, row stride T | 1) and its register-resident rows end; the sentence length n is
+ * bounded by the workspace alone.
+ * -22 and nothing written for T outside [1, 192], start / stop outside [0, T), negative B or n, and a null (or not 16-byte aligned)
+ * ws when B * n > 0.
+ *   kbner_crf_wide_viterbi    _viterbi_decode :1248-1327 (from _obtain_labels :1193-1210); bit-exact tag indices.  ws:
+ *                             kbner_crf_wide_viterbi_ws_bytes(B, n, T) bytes (fp32 Viterbi scores + u8 backpointers)
+ *   kbner_crf_wide_nll_fwd    _forward_alg :1329-1394 + FastSequenceTagger._score_sentence :2544-2591
+ *   kbner_crf_wide_nll_bwd    their autograd backward (loss.backward(), flair/trainers/finetune_trainer.py:957)
+ *   kbner_crf_wide_posterior  the predict_posterior branch of _obtain_labels (:1182-1192, _backward_alg :1396-1470) */
+#define KBNER_CRF_WIDE_MAXT 192
+size_t kbner_crf_wide_viterbi_ws_bytes(int B, int n, int T);
+int kbner_crf_wide_viterbi(const float* emit, const float* trans, const int* lens, int B, int n, int T, int start, int stop,
+                           int* tags, float* conf, int* popped, void* ws, void* stream);
+int kbner_crf_wide_nll_fwd(const float* emit, const float* trans, const int* tags, const int* lens, int B, int n, int T, int start,
+                           int stop, float* logz, float* gold, float* alpha, void* stream);
+int kbner_crf_wide_nll_bwd(const float* emit, const float* trans, const int* tags, const int* lens, const float* alpha,
+                           const float* logz, const float* dloss, int B, int n, int T, int start, int stop, float* demit,
+                           float* dtrans, void* stream);
+int kbner_crf_wide_posterior(const float* emit, const float* trans, const int* lens, const float* alpha, const float* logz, int B,
+                             int n, int T, int start, int stop, float* marg, void* stream);
+
 /* Multi-view ("cooperative learning") posterior distillation between two views of the same sentences -- the `distill_posterior`
    branch of FastSequenceTagger._calculate_multi_view_loss (flair/models/sequence_tagger_model.py:2080-2093, loss form
    :2384-2398), called by ModelFinetuner.train (flair/trainers/finetune_trainer.py:959-966).  loss[b] = T^2 * sum_i KL(softmax(
@@ -152,7 +178,8 @@ int kbner_gather_rows_drop(const kbner_bf16* src, const int* idx, kbner_bf16* ou
                            uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 int kbner_scatter_rows_drop(const kbner_bf16* dout, const int* idx, kbner_bf16* dsrc, int R, int H, int n, uint32_t seed_e,
                             uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
-/* self.linear, sequence_tagger_model.py:1027: out f32[R,T] = x bf16[R,H] . w f32[T,H]^T + bias */
+/* self.linear, sequence_tagger_model.py:1027: out f32[R,T] = x bf16[R,H] . w f32[T,H]^T + bias; T <= 192 (bwd_dw walks the tags in
+ * blocks of 64 above 64 tags) */
 int kbner_head_fwd(const kbner_bf16* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream);
 int kbner_head_bwd_dx(const float* de, const float* w, kbner_bf16* dx, int R, int H, int T, void* stream);
 int kbner_head_bwd_dw(const float* de, const kbner_bf16* x, float* dw, float* db, int R, int H, int T, void* stream);

@@ -217,7 +217,8 @@ int kbner_scatter_add_rows_f32(const float* rows, const int* idx, float* dst, in
 
 // ---- the emission head
 
-#define HEAD_MAXT 64
+#define HEAD_MAXT 64        // tags per thread in head_bwd_dw_kernel; wider tag sets walk blocks of HEAD_MAXT tags
+#define HEAD_WIDE_MAXT 192  // the widest tag set the head takes (the wide CRF kernels of csrc/crf_wide.hip end there)
 #define HEAD_NCH 2        // 16-byte chunks of a row per lane in the kernels that hold the row in registers
 #define HEAD_MAXH 1024    // the widest row they take
 static_assert(HEAD_MAXH == 64 * 8 * HEAD_NCH, "HEAD_NCH chunks of 64 lanes x 8 columns cover HEAD_MAXH columns");
@@ -384,9 +385,51 @@ __global__ __launch_bounds__(256) void head_bwd_dw_kernel(const float* __restric
   }
 }
 
+// The same for T > HEAD_MAXT (tag sets of 65 to 192 tags): blockIdx.z walks the tags in blocks of HEAD_MAXT; a block stages and
+// accumulates its own HEAD_MAXT tags (zero-padded behind T) and adds its own rows of dw and entries of db, so every db[t] still
+// receives one add per row block.  A kernel of its own, so that the instantiations above stay what they were, to the byte.
+__global__ __launch_bounds__(256) void head_bwd_dw_blk_kernel(const float* __restrict__ de, const bf16_t* __restrict__ x,
+                                                              float* __restrict__ dw, float* __restrict__ db, int R, int H, int T) {
+  constexpr int TMAX = HEAD_MAXT, RB = 64;
+  __shared__ __attribute__((aligned(16))) float sde[RB * TMAX];
+  const int h = blockIdx.x * 256 + threadIdx.x;
+  const int r0 = blockIdx.y * RB;
+  const int nr = min(RB, R - r0);
+  const int t0 = blockIdx.z * TMAX;
+  for (int i = threadIdx.x; i < RB * TMAX; i += 256) {
+    const int r = i / TMAX, t = i % TMAX;
+    sde[i] = (r < nr && t0 + t < T) ? de[(size_t)(r0 + r) * T + t0 + t] : 0.0f;
+  }
+  __syncthreads();
+  float acc[TMAX];
+#pragma unroll
+  for (int t = 0; t < TMAX; ++t) acc[t] = 0.0f;
+  if (h < H) {
+    for (int r = 0; r < nr; ++r) {
+      const float xv = bf2f(x[(size_t)(r0 + r) * H + h]);
+#pragma unroll
+      for (int t4 = 0; t4 < TMAX / 4; ++t4) {
+        const float4 d = *reinterpret_cast<const float4*>(&sde[r * TMAX + t4 * 4]);
+        acc[t4 * 4 + 0] += d.x * xv;
+        acc[t4 * 4 + 1] += d.y * xv;
+        acc[t4 * 4 + 2] += d.z * xv;
+        acc[t4 * 4 + 3] += d.w * xv;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TMAX; ++t)
+      if (t0 + t < T) atomicAdd(dw + (size_t)(t0 + t) * H + h, acc[t]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < TMAX && t0 + threadIdx.x < T) {
+    float s = 0.0f;
+    for (int r = 0; r < nr; ++r) s += sde[r * TMAX + threadIdx.x];
+    atomicAdd(db + t0 + threadIdx.x, s);
+  }
+}
+
 extern "C" {
 int kbner_head_fwd(const bf16_t* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= 8192 && T > 0 && T <= HEAD_MAXT);
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= 8192 && T > 0 && T <= HEAD_WIDE_MAXT);
   if (R == 0) return 0;
   if (H <= HEAD_MAXH && R <= 512)
     hipLaunchKernelGGL(head_fwd_rt_kernel, dim3((R * T + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, R, H, T);
@@ -398,14 +441,14 @@ int kbner_head_fwd(const bf16_t* x, const float* w, const float* bias, float* ou
 }
 
 int kbner_head_bwd_dx(const float* de, const float* w, bf16_t* dx, int R, int H, int T, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= HEAD_MAXH && T > 0 && T <= HEAD_MAXT);
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= HEAD_MAXH && T > 0 && T <= HEAD_WIDE_MAXT);
   if (R == 0) return 0;
   hipLaunchKernelGGL(head_bwd_dx_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, de, w, dx, R, H, T);
   KBNER_LAUNCH_RET();
 }
 
 int kbner_head_bwd_dw(const float* de, const bf16_t* x, float* dw, float* db, int R, int H, int T, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && T > 0 && T <= HEAD_MAXT);
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && T > 0 && T <= HEAD_WIDE_MAXT);
   if (R == 0) return 0;
   if (T <= 32 && R <= 512)
     hipLaunchKernelGGL((head_bwd_dw_kernel<32, 16>), dim3((H + 255) / 256, (R + 15) / 16), dim3(256), 0, (hipStream_t)stream, de, x, dw,
@@ -413,9 +456,12 @@ int kbner_head_bwd_dw(const float* de, const bf16_t* x, float* dw, float* db, in
   else if (T <= 32)
     hipLaunchKernelGGL(head_bwd_dw_kernel<32>, dim3((H + 255) / 256, (R + 63) / 64), dim3(256), 0, (hipStream_t)stream, de, x, dw,
                        db, R, H, T);
-  else
+  else if (T <= HEAD_MAXT)
     hipLaunchKernelGGL(head_bwd_dw_kernel<HEAD_MAXT>, dim3((H + 255) / 256, (R + 63) / 64), dim3(256), 0, (hipStream_t)stream, de, x,
                        dw, db, R, H, T);
+  else
+    hipLaunchKernelGGL(head_bwd_dw_blk_kernel, dim3((H + 255) / 256, (R + 63) / 64, (T + HEAD_MAXT - 1) / HEAD_MAXT), dim3(256), 0,
+                       (hipStream_t)stream, de, x, dw, db, R, H, T);
   KBNER_LAUNCH_RET();
 }
 }  // extern "C"

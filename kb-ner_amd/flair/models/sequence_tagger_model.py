@@ -36,6 +36,10 @@ _UNSUPPORTED_TRUE = ("use_mfvi", "use_cnn", "biaf_attention", "use_language_atte
                      "train_initial_hidden_state")
 
 
+NARROW_MAX_TAGS = 64    # one tag per lane of one wave: the softmax head and every distillation kernel (those at 32)
+WIDE_MAX_TAGS = 192     # kbner.ops.CRF_WIDE_MAXT: the workgroup-wide CRF kernels and the emission head
+
+
 class SequenceTagger(flair.nn.Model):
     def __init__(self, hidden_size: int, embeddings, tag_dictionary: Dictionary, tag_type: str, use_crf: bool = True,
                  use_mfvi: bool = False, use_rnn: bool = True, use_cnn: bool = False, rnn_layers: int = 1, dropout: float = 0.0,
@@ -117,6 +121,22 @@ class SequenceTagger(flair.nn.Model):
             raise ValueError("crf_attention / distill_with_gold weight the n-best paths of distill_crf: enable distill_crf")
         if distill_with_gold and not crf_attention:
             raise ValueError("distill_with_gold reweights the crf_attention path weights (sequence_tagger_model.py:2282-2304): enable crf_attention")
+        # tag sets of 65 to 192 tags run on the workgroup-wide CRF kernels (csrc/crf_wide.hip) and the tag-blocked emission head: the
+        # CRF tagger trains, evaluates, predicts and decodes posteriors.  The softmax head, the emission KL (64 tags) and the
+        # multi-view / distillation scans and their n-best teacher labels (32 tags) have single-wave kernels only: refused here, by
+        # name, instead of a KbnerError(-22) from inside a step.  Nothing changes up to 64 tags.
+        n_tags = len(tag_dictionary)
+        if n_tags > WIDE_MAX_TAGS:
+            raise NotImplementedError("a tag dictionary of %d items: the CRF kernels keep the transition matrix in LDS and end at %d "
+                                      "tags" % (n_tags, WIDE_MAX_TAGS))
+        if n_tags > NARROW_MAX_TAGS:
+            narrow = [("use_crf=False", not use_crf, 64), ("multi_view_training", multi_view_training, 32),
+                      ("distill_crf", distill_crf, 32), ("distill_posterior", distill_posterior, 32),
+                      ("distill_exact", distill_exact, 32), ("distill_emission", distill_emission, 64)]
+            for name, on, limit in narrow:
+                if on:
+                    raise NotImplementedError("%s with a tag dictionary of %d items: its kernels end at %d tags (the CRF tagger "
+                                              "itself takes up to %d)" % (name, n_tags, limit, WIDE_MAX_TAGS))
         self.hidden_size = hidden_size
         self.embeddings = embeddings
         self.tag_dictionary = tag_dictionary

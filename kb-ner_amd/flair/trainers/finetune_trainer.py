@@ -181,6 +181,11 @@ class ModelFinetuner:
         for teacher in teachers:
             if m.tag_dictionary.item2idx != teacher.tag_dictionary.item2idx:
                 raise ValueError("the tag_dictionaries of the teacher and student are not same")
+            if len(teacher.tag_dictionary) > 64:
+                # kbner_crf_viterbi_nbest / kbner_crf_fb_score / kbner_crf_pair_posterior are single-wave kernels
+                raise NotImplementedError("teacher targets (n-best paths, posterior scores, pairwise posteriors) of a teacher with a "
+                                          "tag dictionary of %d items: the n-best decoder ends at 64 tags, the distillation scans at 32"
+                                          % len(teacher.tag_dictionary))
             teacher.eval()
             for index, train_data in enumerate(coupled_train_data):
                 if self.corpus.targets[index] not in getattr(teacher, "targets", set(self.corpus.targets)):

@@ -36,6 +36,15 @@ def _chk(t, dtype, name):
 
 
 # ---------------------------------------------------------------- CRF
+CRF_NARROW_MAXT = 64    # csrc/crf.hip: one tag per lane of one wave
+CRF_WIDE_MAXT = 192     # csrc/crf_wide.hip: one workgroup per sentence, transitions in LDS (KBNER_CRF_WIDE_MAXT)
+
+
+def _crf(name, T):
+    """entry point of the tag count: T <= 64 the single-wave kernels, above that the workgroup-wide ones"""
+    return name if T <= CRF_NARROW_MAXT else name.replace("kbner_crf_", "kbner_crf_wide_")
+
+
 def crf_viterbi(emit, trans, lens, start, stop, want_popped=False):
     """emit f32[B,n,T], trans f32[T,T], lens i32[B] -> tags i32[B,n], conf f32[B,n] (, popped i32[B])"""
     _chk(emit, F32, "emit"); _chk(trans, F32, "trans"); _chk(lens, I32, "lens")
@@ -43,8 +52,13 @@ def crf_viterbi(emit, trans, lens, start, stop, want_popped=False):
     tags = torch.empty((B, n), dtype=I32, device=emit.device)
     conf = torch.empty((B, n), dtype=F32, device=emit.device)
     popped = torch.empty((B,), dtype=I32, device=emit.device) if want_popped else None
-    L.call("kbner_crf_viterbi", ptr(emit), ptr(trans), ptr(lens), B, n, T, start, stop, ptr(tags), ptr(conf), ptr(popped),
-           stream_ptr())
+    if T <= CRF_NARROW_MAXT:
+        L.call("kbner_crf_viterbi", ptr(emit), ptr(trans), ptr(lens), B, n, T, start, stop, ptr(tags), ptr(conf), ptr(popped),
+               stream_ptr())
+    else:
+        ws = torch.empty(max(16, L.load().kbner_crf_wide_viterbi_ws_bytes(B, n, T)), dtype=torch.uint8, device=emit.device)
+        L.call("kbner_crf_wide_viterbi", ptr(emit), ptr(trans), ptr(lens), B, n, T, start, stop, ptr(tags), ptr(conf), ptr(popped),
+               ptr(ws), stream_ptr())
     return (tags, conf, popped) if want_popped else (tags, conf)
 
 
@@ -54,7 +68,7 @@ def crf_nll_fwd(emit, trans, tags, lens, start, stop):
     logz = torch.empty((B,), dtype=F32, device=emit.device)
     gold = torch.empty((B,), dtype=F32, device=emit.device)
     alpha = torch.empty((B, n + 1, T), dtype=F32, device=emit.device)
-    L.call("kbner_crf_nll_fwd", ptr(emit), ptr(trans), ptr(tags), ptr(lens), B, n, T, start, stop, ptr(logz), ptr(gold),
+    L.call(_crf("kbner_crf_nll_fwd", T), ptr(emit), ptr(trans), ptr(tags), ptr(lens), B, n, T, start, stop, ptr(logz), ptr(gold),
            ptr(alpha), stream_ptr())
     return logz, gold, alpha
 
@@ -64,7 +78,7 @@ def crf_nll_bwd(emit, trans, tags, lens, alpha, logz, dloss, start, stop, dtrans
     _chk(dloss, F32, "dloss"); _chk(dtrans, F32, "dtrans")
     B, n, T = emit.shape
     demit = torch.empty_like(emit)
-    L.call("kbner_crf_nll_bwd", ptr(emit), ptr(trans), ptr(tags), ptr(lens), ptr(alpha), ptr(logz), ptr(dloss), B, n, T, start,
+    L.call(_crf("kbner_crf_nll_bwd", T), ptr(emit), ptr(trans), ptr(tags), ptr(lens), ptr(alpha), ptr(logz), ptr(dloss), B, n, T, start,
            stop, ptr(demit), ptr(dtrans), stream_ptr())
     return demit
 
@@ -88,7 +102,7 @@ def crf_posterior(emit, trans, lens, start, stop):
     zeros = torch.zeros((B, n), dtype=I32, device=emit.device)
     logz, _, alpha = crf_nll_fwd(emit, trans, zeros, lens, start, stop)
     marg = torch.empty_like(emit)
-    L.call("kbner_crf_posterior", ptr(emit), ptr(trans), ptr(lens), ptr(alpha), ptr(logz), B, n, T, start, stop, ptr(marg),
+    L.call(_crf("kbner_crf_posterior", T), ptr(emit), ptr(trans), ptr(lens), ptr(alpha), ptr(logz), B, n, T, start, stop, ptr(marg),
            stream_ptr())
     return marg
 
