@@ -178,8 +178,26 @@ int kbner_gather_rows_drop(const kbner_bf16* src, const int* idx, kbner_bf16* ou
                            uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 int kbner_scatter_rows_drop(const kbner_bf16* dout, const int* idx, kbner_bf16* dsrc, int R, int H, int n, uint32_t seed_e,
                             uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+/* Encoder layer selection of TransformerWordEmbeddings (layers="-1,-2,-3,-4" / 'all', use_scalar_mix): the gather of the first
+ * sub-token rows over k hidden states at once, replacing the per-layer selection, torch.cat and torch.mean of
+ * flair/embeddings.py:2983-2991, 3315-3343 (the reference's use_scalar_mix IS torch.mean over the selected rows, :3337; its
+ * ScalarMix module is commented out) and the autograd graph behind them.  srcs: HOST array of k device pointers (1 <= k <= 32), each a
+ * bf16 [*, H] matrix; the pointers travel in the launch's arguments (no device allocation; the call can be graph-captured).
+ *   mean == 0: out bf16 [R, k*H], out[r, j*H + h] = idx[r] >= 0 ? bf16(src_j[idx[r], h] * m[r, j*H + h]) : 0          (k*H <= 8192)
+ *   mean != 0: out bf16 [R, H],   out[r, h] = idx[r] >= 0 ? bf16((sum_j src_j[idx[r], h], fp32, j ascending) * fp32(1/k) * m[r, h]) : 0
+ * m = m_e * m_l as for kbner_gather_rows_drop, keyed by the column of the OUTPUT row: element (r, column) of site (seed_e, thresh_e),
+ * element (r / n, column) of site (seed_l, thresh_l); a threshold of 0 disables its site.  H % 8 == 0, n >= 1, R % n == 0. */
+int kbner_gather_rows_layers(const kbner_bf16* const* srcs, int k, int mean, const int* idx, kbner_bf16* out, int R, int H, int n,
+                             uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+/* its backward for ONE selected hidden state (autograd's backward of the select / cat / mean of flair/embeddings.py:3315-3343): columns
+ * [col0, col0 + H) of the feature gradient dout (row stride ld) are ADDED to the rows of that state's gradient the index names:
+ *   dst[idx[r], h] = bf16(f32(dst[idx[r], h]) + f32(dout[r*ld + col0 + h]) * (m[r, col0 + h] * scale))      for idx[r] >= 0
+ * (unique indices: a plain read-modify-write; other rows are not touched).  Concatenation: col0 = j*H, scale = 1; mean: col0 = 0,
+ * ld = H, scale = 1/k.  ld % 8 == 0, col0 % 8 == 0, col0 + H <= ld. */
+int kbner_scatter_add_rows_ld(const kbner_bf16* dout, int ld, int col0, const int* idx, kbner_bf16* dst, int R, int H, float scale,
+                              int n, uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 /* self.linear, sequence_tagger_model.py:1027: out f32[R,T] = x bf16[R,H] . w f32[T,H]^T + bias; T <= 192 (bwd_dw walks the tags in
- * blocks of 64 above 64 tags) */
+ * blocks of 64 above 64 tags); H <= 8192 (rows wider than 1024 columns are walked in 512-column chunks) */
 int kbner_head_fwd(const kbner_bf16* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream);
 int kbner_head_bwd_dx(const float* de, const float* w, kbner_bf16* dx, int R, int H, int T, void* stream);
 int kbner_head_bwd_dw(const float* de, const kbner_bf16* x, float* dw, float* db, int R, int H, int T, void* stream);

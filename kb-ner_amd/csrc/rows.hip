@@ -94,6 +94,117 @@ __global__ __launch_bounds__(256) void rows_drop_kernel(const bf16_t* __restrict
   }
 }
 
+// Encoder layer selection (TransformerWordEmbeddings(layers=..., use_scalar_mix=...), flair/embeddings.py:2983-2991, 3315-3343): the token
+// feature is the first-sub-token row of k hidden states, concatenated ([R, k * H]) or averaged (torch.mean over the k rows, :3337;
+// [R, H]), with the head's two dropout sites of rows_drop_kernel keyed by the OUTPUT column of the W-wide row:
+//     concat: out[r, j * H + h] = idx[r] >= 0 ? bf16(src_j[idx[r], h] * m[r, j * H + h]) : 0
+//     mean  : out[r, h]         = idx[r] >= 0 ? bf16((sum_j src_j[idx[r], h], fp32, j ascending) * fp32(1 / k) * m[r, h]) : 0
+// The k source pointers travel BY VALUE in the kernel arguments (as ColsumBatch does): nothing is allocated on the device and the launch
+// can be captured into a graph.  Same shape as rows_drop_kernel: one wave per row, 16-byte accesses, the 512-column chunk of the OUTPUT
+// row as the outer loop, so the chunk's source (concat: one source per 8 columns, H % 8 == 0) and its column keys stay in registers over
+// the rows.  DROP = false (both sites off): the mask code is compiled out -- a copy (concat) or the plain mean.
+#define LAYERS_MAX 32
+struct LayerSrcs {
+  const bf16_t* p[LAYERS_MAX];
+};
+template <bool MEAN, bool DROP>
+__global__ __launch_bounds__(256) void gather_rows_layers_kernel(const LayerSrcs srcs, int k, const int* __restrict__ idx,
+                                                                 bf16_t* __restrict__ out, int R, int H, int n, uint32_t seed_e,
+                                                                 uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l) {
+  const int lane = threadIdx.x % 64;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + threadIdx.x / 64);
+  const int nwave = gridDim.x * 4;
+  const int W = MEAN ? H : k * H;
+  const float scale = drop_scale(thresh_e) * drop_scale(thresh_l);
+  const float inv_k = 1.0f / (float)k;
+  for (int c0 = lane * 8; c0 < W; c0 += 512) {
+    const int h0 = MEAN ? c0 : c0 % H;
+    const bf16_t* __restrict__ src = srcs.p[MEAN ? 0 : c0 / H];
+    uint32_t cke[8], ckl[8];
+    if (DROP) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        cke[j] = drop_colkey(seed_e, (uint32_t)(c0 + j));
+        ckl[j] = drop_colkey(seed_l, (uint32_t)(c0 + j));
+      }
+    }
+    for (int r = wave; r < R; r += nwave) {
+      const int s = idx[r];
+      uint4 u = make_uint4(0, 0, 0, 0);
+      if (s >= 0) {
+        u = *reinterpret_cast<const uint4*>(src + (size_t)s * H + h0);
+        if (MEAN || DROP) {
+          float v[8];
+          unpack8bf(u, v);
+          if (MEAN) {
+            for (int q = 1; q < k; ++q) {
+              float x[8];
+              unpack8bf(*reinterpret_cast<const uint4*>(srcs.p[q] + (size_t)s * H + h0), x);
+#pragma unroll
+              for (int j = 0; j < 8; ++j) v[j] += x[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= inv_k;
+          }
+          if (DROP) {
+            const uint32_t rke = drop_rowkey(seed_e, (uint32_t)r);
+            const uint32_t rkl = drop_rowkey(seed_l, (uint32_t)(r / n));
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              v[j] *= (drop_keep(rke, cke[j], thresh_e) && drop_keep(rkl, ckl[j], thresh_l)) ? scale : 0.0f;
+          }
+          u = pack8bf(v);
+        }
+      }
+      *reinterpret_cast<uint4*>(out + (size_t)r * W + c0) = u;
+    }
+  }
+}
+
+// The backward of one source's share: columns [col0, col0 + H) of the W-wide feature gradient (row stride ld) are ADDED to the rows of
+// that source's gradient idx names -- added, because the matrix already holds what the layers above sent down:
+//     dst[idx[r], h] = bf16(f32(dst[idx[r], h]) + f32(dout[r * ld + col0 + h]) * (m[r, col0 + h] * scale))      for idx[r] >= 0
+// (m as above, keyed by the column of the W-wide row; scale = 1 for a concatenated block, 1 / k under the mean).  Indices are unique
+// (one first sub-token per word token): a plain read-modify-write; rows idx does not name are not touched.
+template <bool DROP>
+__global__ __launch_bounds__(256) void scatter_add_rows_ld_kernel(const bf16_t* __restrict__ dout, int ld, int col0,
+                                                                  const int* __restrict__ idx, bf16_t* __restrict__ dst, int R, int H,
+                                                                  float scale, int n, uint32_t seed_e, uint32_t thresh_e,
+                                                                  uint32_t seed_l, uint32_t thresh_l) {
+  const int lane = threadIdx.x % 64;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + threadIdx.x / 64);
+  const int nwave = gridDim.x * 4;
+  const float dscale = drop_scale(thresh_e) * drop_scale(thresh_l);
+  for (int h0 = lane * 8; h0 < H; h0 += 512) {
+    uint32_t cke[8], ckl[8];
+    if (DROP) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        cke[j] = drop_colkey(seed_e, (uint32_t)(col0 + h0 + j));
+        ckl[j] = drop_colkey(seed_l, (uint32_t)(col0 + h0 + j));
+      }
+    }
+    for (int r = wave; r < R; r += nwave) {
+      const int s = idx[r];
+      if (s < 0) continue;
+      float d[8], a[8];
+      unpack8bf(*reinterpret_cast<const uint4*>(dout + (size_t)r * ld + col0 + h0), d);
+      unpack8bf(*reinterpret_cast<const uint4*>(dst + (size_t)s * H + h0), a);
+      if (DROP) {
+        const uint32_t rke = drop_rowkey(seed_e, (uint32_t)r);
+        const uint32_t rkl = drop_rowkey(seed_l, (uint32_t)(r / n));
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          a[j] += d[j] * (((drop_keep(rke, cke[j], thresh_e) && drop_keep(rkl, ckl[j], thresh_l)) ? dscale : 0.0f) * scale);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] += d[j] * scale;
+      }
+      *reinterpret_cast<uint4*>(dst + (size_t)s * H + h0) = pack8bf(a);
+    }
+  }
+}
+
 // fp32 row gather (evaluation path: compaction of the [B*n, T] emissions to the non-S-X rows before Viterbi / CRF loss):
 // out[r,:] = idx[r] >= 0 ? src[idx[r],:] : 0
 __global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx,
@@ -181,6 +292,45 @@ int kbner_scatter_rows_drop(const bf16_t* dout, const int* idx, bf16_t* dsrc, in
   else
     hipLaunchKernelGGL(rows_drop_kernel<true>, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, idx, dsrc, R, H, n, seed_e,
                        thresh_e, seed_l, thresh_l);
+  KBNER_LAUNCH_RET();
+}
+
+// srcs: HOST array of k device pointers (bf16 [*, H] each), copied into the launch's arguments
+int kbner_gather_rows_layers(const bf16_t* const* srcs, int k, int mean, const int* idx, bf16_t* out, int R, int H, int n,
+                             uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream) {
+  KBNER_CHECK_ARG(srcs != nullptr && k >= 1 && k <= LAYERS_MAX && R >= 0 && H > 0 && H % 8 == 0 && H <= 8192 && n >= 1 && R % n == 0);
+  KBNER_CHECK_ARG(mean != 0 || (long long)k * H <= 8192);
+  LayerSrcs b;
+  for (int i = 0; i < LAYERS_MAX; ++i) {
+    b.p[i] = srcs[i < k ? i : 0];
+    KBNER_CHECK_ARG(b.p[i] != nullptr);
+  }
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(idx != nullptr && out != nullptr);
+  const bool drop = thresh_e != 0 || thresh_l != 0;
+#define LAYERS_LAUNCH(MEAN, DROP)                                                                                                  \
+  hipLaunchKernelGGL((gather_rows_layers_kernel<MEAN, DROP>), dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, b, k, idx, out, R, \
+                     H, n, seed_e, thresh_e, seed_l, thresh_l)
+  if (mean && drop) LAYERS_LAUNCH(true, true);
+  else if (mean) LAYERS_LAUNCH(true, false);
+  else if (drop) LAYERS_LAUNCH(false, true);
+  else LAYERS_LAUNCH(false, false);
+#undef LAYERS_LAUNCH
+  KBNER_LAUNCH_RET();
+}
+
+int kbner_scatter_add_rows_ld(const bf16_t* dout, int ld, int col0, const int* idx, bf16_t* dst, int R, int H, float scale, int n,
+                              uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && ld > 0 && ld % 8 == 0 && col0 >= 0 && col0 % 8 == 0 && col0 + H <= ld && n >= 1 &&
+                  R % n == 0);
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(dout != nullptr && idx != nullptr && dst != nullptr);
+  if (thresh_e == 0 && thresh_l == 0)
+    hipLaunchKernelGGL(scatter_add_rows_ld_kernel<false>, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, ld, col0, idx, dst,
+                       R, H, scale, n, seed_e, thresh_e, seed_l, thresh_l);
+  else
+    hipLaunchKernelGGL(scatter_add_rows_ld_kernel<true>, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, dout, ld, col0, idx, dst,
+                       R, H, scale, n, seed_e, thresh_e, seed_l, thresh_l);
   KBNER_LAUNCH_RET();
 }
 
@@ -340,6 +490,30 @@ __global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restric
   }
 }
 
+// head_bwd_dx_kernel for wide rows (H > HEAD_MAXH: the head behind a concatenation of encoder layers, linear(k * hidden -> T)): the row is
+// walked in 512-column chunks, as head_fwd_wide_kernel walks it, each chunk summing the T tags in the same order
+__global__ __launch_bounds__(256) void head_bwd_dx_wide_kernel(const float* __restrict__ de, const float* __restrict__ w,
+                                                               bf16_t* __restrict__ dx, int R, int H, int T) {
+  const int lane = threadIdx.x % 64;
+  const int wave = blockIdx.x * 4 + threadIdx.x / 64;
+  const int nwave = gridDim.x * 4;
+  for (int r = wave; r < R; r += nwave) {
+    for (int h0 = lane * 8; h0 < H; h0 += 512) {
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
+      for (int t = 0; t < T; ++t) {
+        const float d = de[(size_t)r * T + t];
+        const float4 a = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0);
+        const float4 b = *reinterpret_cast<const float4*>(w + (size_t)t * H + h0 + 4);
+        acc[0] += d * a.x; acc[1] += d * a.y; acc[2] += d * a.z; acc[3] += d * a.w;
+        acc[4] += d * b.x; acc[5] += d * b.y; acc[6] += d * b.z; acc[7] += d * b.w;
+      }
+      *reinterpret_cast<uint4*>(dx + (size_t)r * H + h0) = pack8bf(acc);
+    }
+  }
+}
+
 // dw[t,h] += sum_r de[r,t] * x[r,h] ; db[t] += sum_r de[r,t]
 // grid = (ceil(H/256), ceil(R/64)); thread owns column h; 64 rows of de staged in LDS.
 // TMAX (32 for T <= 32: the 29 tags of the KB-NER dictionaries; 64 otherwise): the staged rows have a FIXED stride of TMAX floats,
@@ -441,9 +615,12 @@ int kbner_head_fwd(const bf16_t* x, const float* w, const float* bias, float* ou
 }
 
 int kbner_head_bwd_dx(const float* de, const float* w, bf16_t* dx, int R, int H, int T, void* stream) {
-  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= HEAD_MAXH && T > 0 && T <= HEAD_WIDE_MAXT);
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && H <= 8192 && T > 0 && T <= HEAD_WIDE_MAXT);
   if (R == 0) return 0;
-  hipLaunchKernelGGL(head_bwd_dx_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, de, w, dx, R, H, T);
+  if (H <= HEAD_MAXH)
+    hipLaunchKernelGGL(head_bwd_dx_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, de, w, dx, R, H, T);
+  else
+    hipLaunchKernelGGL(head_bwd_dx_wide_kernel, dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, de, w, dx, R, H, T);
   KBNER_LAUNCH_RET();
 }
 

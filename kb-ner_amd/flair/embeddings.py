@@ -135,6 +135,9 @@ def _load_hf_dir(model_dir):
     return config, out
 
 
+MAX_EMBEDDING_WIDTH = 8192   # the widest token feature the emission head's kernels take (kbner.engine.HEAD_MAX_WIDTH)
+
+
 class TransformerWordEmbeddings(TokenEmbeddings):
     def __init__(self, model: str = "xlm-roberta-large", layers: str = "-1", pooling_operation: str = "first", batch_size: int = 1,
                  use_scalar_mix: bool = False, fine_tune: bool = False, allow_long_sentences: bool = True, stride: int = -1,
@@ -146,8 +149,9 @@ class TransformerWordEmbeddings(TokenEmbeddings):
         if not os.path.isdir(model):
             raise FileNotFoundError("TransformerWordEmbeddings(model=%r): a local HF directory is required (no network); it must "
                                     "hold the tokenizer files, config.json and model.safetensors / pytorch_model.bin" % model)
-        if [int(x) for x in str(layers).split(",")] != [-1] or pooling_operation != "first" or use_scalar_mix:
-            raise NotImplementedError("only layers='-1', pooling_operation='first' (the KB-NER configs) are on the MI355X path")
+        if pooling_operation != "first":
+            raise NotImplementedError("pooling_operation=%r: only 'first' (the KB-NER configs) is on the MI355X path; the layer "
+                                      "selection (`layers`, `use_scalar_mix`) is" % (pooling_operation,))
         if document_extraction or ext_doc or sentence_feat:
             raise NotImplementedError("document_extraction / ext_doc / sentence_feat are outside the hot path (SURVEY.md §8f-3); "
                                       "v2_doc (document windows) is supported")
@@ -158,9 +162,33 @@ class TransformerWordEmbeddings(TokenEmbeddings):
         config, sd = _load_hf_dir(model)
         self.model = _EncoderHandle(config, sd)
         self.name = str(model) if embedding_name is None else embedding_name
-        self.layer_indexes = [-1]
+        # layer selection (the reference's :2983-2991): indices into the L + 1 hidden states -- 0 the embedding LayerNorm's output, i
+        # layer i's, negative from the end -- in the order given, duplicates kept; 'all' = 0 .. L.  The token feature is the
+        # concatenation of the selected layers' first-sub-token rows (k * hidden columns) or, with use_scalar_mix, their mean (the
+        # reference's torch.mean, :3337: hidden columns, no parameter).  The default here stays '-1' (the reference's is the last four)
+        n_states = int(config.num_hidden_layers) + 1
+        if str(layers).strip() == "all":
+            self.layer_indexes = list(range(n_states))
+        else:
+            try:
+                self.layer_indexes = [int(x) for x in str(layers).split(",")]
+            except ValueError:
+                raise ValueError("layers=%r: a comma-separated list of layer indices, or 'all'" % (layers,))
+        for li in self.layer_indexes:
+            if not -n_states <= li < n_states:
+                raise ValueError("layers=%r: layer index %d is outside the %d hidden states of %s (valid: %d .. %d)"
+                                 % (layers, li, n_states, model, -n_states, n_states - 1))
+        if not 1 <= len(self.layer_indexes) <= 32:
+            raise ValueError("layers=%r: a selection names 1 to 32 hidden states" % (layers,))
         self.pooling_operation = pooling_operation
-        self.use_scalar_mix = False
+        self.use_scalar_mix = bool(use_scalar_mix)
+        width = int(config.hidden_size) * (1 if self.use_scalar_mix else len(self.layer_indexes))
+        if width > MAX_EMBEDDING_WIDTH:
+            raise NotImplementedError("layers=%r concatenates %d hidden states into a token feature of width %d; the emission head "
+                                      "takes at most %d columns -- select fewer layers, or set use_scalar_mix: true (their mean, "
+                                      "width %d)" % (layers, len(self.layer_indexes), width, MAX_EMBEDDING_WIDTH, int(config.hidden_size)))
+        log.info("TransformerWordEmbeddings(%s): layers %s%s -> token features of width %d", model,
+                 ",".join(str(i) for i in self.layer_indexes), " (mean: use_scalar_mix)" if self.use_scalar_mix else "", width)
         self.fine_tune = fine_tune
         self.static_embeddings = not fine_tune
         self.batch_size = batch_size
@@ -183,7 +211,12 @@ class TransformerWordEmbeddings(TokenEmbeddings):
 
     @property
     def embedding_length(self) -> int:
-        return self._hidden
+        return self._hidden if self.use_scalar_mix else len(self.layer_indexes) * self._hidden
+
+    @property
+    def layers(self) -> str:
+        """the selection as the `layers` string that reproduces it"""
+        return ",".join(str(i) for i in self.layer_indexes)
 
     # ------------------------------------------------------------------ tokenisation (host, integers only)
     @staticmethod

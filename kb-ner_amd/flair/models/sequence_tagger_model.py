@@ -206,7 +206,10 @@ class SequenceTagger(flair.nn.Model):
                               layer_norm_eps=getattr(hc, "layer_norm_eps", 1e-5),
                               hidden_dropout_prob=float(getattr(hc, "hidden_dropout_prob", 0.1)),
                               attention_probs_dropout_prob=float(getattr(hc, "attention_probs_dropout_prob", 0.1)))
-        self.engine = E.Tagger(cfg, self.tagset_size, self.start_idx, self.stop_idx, device=flair.device)
+        # the embedding's layer selection (TransformerWordEmbeddings(layers=..., use_scalar_mix=...)): the head is W = embedding_length wide
+        self.engine = E.Tagger(cfg, self.tagset_size, self.start_idx, self.stop_idx, device=flair.device,
+                               layers=tuple(getattr(self._emb, "layer_indexes", (-1,))),
+                               layer_mean=bool(getattr(self._emb, "use_scalar_mix", False)))
         self.engine.use_crf = self.use_crf
         # dropout streams differ per data-parallel rank (each rank sees different sentences anyway)
         self.engine.seed_dropout(int(torch.initial_seed() % (2 ** 31)) + 7919 * int(os.environ.get("RANK", "0")))
@@ -214,9 +217,9 @@ class SequenceTagger(flair.nn.Model):
         self.engine.head_dropout, self.engine.locked_dropout = self.use_dropout, self.use_locked_dropout
         self.engine.load_hf_state_dict(self._emb.model.state_dict())
         g = torch.Generator().manual_seed(int(torch.initial_seed() % (2 ** 31)))
-        H = cfg.hidden_size
-        bound = 1.0 / (H ** 0.5)
-        self.engine.set_param("linear.weight", (torch.rand(self.tagset_size, H, generator=g) * 2 - 1) * bound)
+        W = self.engine.W    # torch.nn.Linear's rule on in_features, which is the feature width
+        bound = 1.0 / (W ** 0.5)
+        self.engine.set_param("linear.weight", (torch.rand(self.tagset_size, W, generator=g) * 2 - 1) * bound)
         self.engine.set_param("linear.bias", (torch.rand(self.tagset_size, generator=g) * 2 - 1) * bound)
         tr = torch.randn(self.tagset_size, self.tagset_size, generator=g)
         tr[self.start_idx, :] = -1e12
@@ -248,6 +251,14 @@ class SequenceTagger(flair.nn.Model):
         them with trained values.  Feature blocks follow sorted(embedding names) -- the order forward() concatenates in (:879-891)."""
         from kbner import stack as K
         embs = list(self.embeddings.embeddings) if hasattr(self.embeddings, "embeddings") else [self.embeddings]
+        from flair.embeddings import TransformerWordEmbeddings
+        for e in embs:
+            if isinstance(e, TransformerWordEmbeddings) and (e.use_scalar_mix or list(e.layer_indexes) not in (
+                    [-1], [int(e.model.config.num_hidden_layers)])):
+                raise NotImplementedError("use_rnn: true with TransformerWordEmbeddings(%s, layers=%r%s): the inference stack keeps its "
+                                          "input layout, one last-layer block per encoder (layers='-1'); the layer selection is "
+                                          "implemented for the fine-tuning tagger (use_rnn: false)"
+                                          % (e.name, e.layers, ", use_scalar_mix=True" if e.use_scalar_mix else ""))
         self._stack_embs = sorted(embs, key=lambda e: e.name)
         blocks = [int(e.embedding_length) for e in self._stack_embs]
         H, D, T = int(self.hidden_size), sum(blocks), self.tagset_size
@@ -1001,6 +1012,7 @@ class SequenceTagger(flair.nn.Model):
             "use_crf": self.use_crf, "use_rnn": False, "remove_x": self.remove_x, "sentence_loss": self.sentence_level_loss,
             "word_dropout": self.use_word_dropout, "dropout": self.use_dropout, "locked_dropout": self.use_locked_dropout,
             "embedding_model_dir": getattr(self._emb, "name", None),
+            "embedding_layers": getattr(self._emb, "layers", "-1"), "embedding_scalar_mix": bool(getattr(self._emb, "use_scalar_mix", False)),
             "trained_epochs": self.trained_epochs,
             # loss switches, so that a model re-loaded as a student (load_pretrained) keeps training the way it was configured
             "temperature": self.temperature, "multi_view_training": self.multi_view_training,
@@ -1012,7 +1024,10 @@ class SequenceTagger(flair.nn.Model):
     @classmethod
     def _init_model_with_state_dict(cls, state):
         from flair.embeddings import StackedEmbeddings, TransformerWordEmbeddings
-        emb = TransformerWordEmbeddings(model=state["embedding_model_dir"], layers="-1", pooling_operation="first", fine_tune=True)
+        # (a state from before the layer selection has neither key: the last layer alone)
+        emb = TransformerWordEmbeddings(model=state["embedding_model_dir"], layers=state.get("embedding_layers", "-1"),
+                                        use_scalar_mix=bool(state.get("embedding_scalar_mix", False)), pooling_operation="first",
+                                        fine_tune=True)
         model = cls(hidden_size=state["hidden_size"], embeddings=StackedEmbeddings([emb]), tag_dictionary=state["tag_dictionary"],
                     tag_type=state["tag_type"], use_crf=bool(state.get("use_crf", True)), use_rnn=False, remove_x=state["remove_x"],
                     sentence_loss=state["sentence_loss"], word_dropout=state.get("word_dropout", 0.0),

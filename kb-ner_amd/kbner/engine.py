@@ -173,9 +173,9 @@ class Arena:
             self.v = torch.zeros_like(self.p)
 
 
-def tagger_specs(cfg, T):
+def tagger_specs(cfg, T, W=None):
     """Arena order: GEMM weights (bf16-shadowed) | embeddings, LN, biases, head | transitions (own lr group,
-    flair/trainers/finetune_trainer.py:552-571)."""
+    flair/trainers/finetune_trainer.py:552-571).  W: width of the token feature the head reads (default: the hidden size)."""
     H, F_, V, P, TV = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size, cfg.max_position_embeddings, cfg.type_vocab_size
     specs = []
     for i in range(cfg.num_hidden_layers):
@@ -188,7 +188,7 @@ def tagger_specs(cfg, T):
                   ("l%d.ln1.g" % i, (H,), False), ("l%d.ln1.b" % i, (H,), False),
                   ("l%d.ffn1.bias" % i, (F_,), False), ("l%d.ffn2.bias" % i, (H,), False),
                   ("l%d.ln2.g" % i, (H,), False), ("l%d.ln2.b" % i, (H,), False)]
-    specs += [("linear.weight", (T, H), False), ("linear.bias", (T,), False), ("transitions", (T, T), False)]
+    specs += [("linear.weight", (T, H if W is None else W), False), ("linear.bias", (T,), False), ("transitions", (T, T), False)]
     return specs
 
 
@@ -273,6 +273,23 @@ class _Acts:
 WGRAD_GROUP = 4
 
 
+HEAD_MAX_WIDTH = 8192   # the widest token feature the emission head's kernels take (csrc/rows.hip)
+
+
+def normalize_layers(layers, L):
+    """TransformerWordEmbeddings' layer_indexes (flair/embeddings.py:2983-2991) as indices 0..L into the L + 1 hidden states: 0 is
+    the embedding LayerNorm's output, i layer i's, -1 the last layer's; order and duplicates are kept."""
+    sel = []
+    for i in layers:
+        i = int(i)
+        if not -(L + 1) <= i <= L:
+            raise ValueError("layer index %d is outside the %d hidden states of this encoder (valid: %d .. %d)" % (i, L + 1, -(L + 1), L))
+        sel.append(i + L + 1 if i < 0 else i)
+    if not 1 <= len(sel) <= 32:
+        raise ValueError("a layer selection names 1 to 32 hidden states (got %d)" % len(sel))
+    return tuple(sel)
+
+
 def _splitk(tiles, Mp):
     """split the token (reduction) dimension of a wgrad GEMM so the launch has >= ~768 workgroups"""
     sk = 1
@@ -287,10 +304,20 @@ class Tagger:
     Reference path: TransformerWordEmbeddings (flair/embeddings.py:2906) -> FastSequenceTagger.forward /
     forward_loss / _calculate_loss (flair/models/sequence_tagger_model.py:844,1899,2426)."""
 
-    def __init__(self, cfg, num_tags, start_idx, stop_idx, device="cuda", inference=False, wgrad_overwrite=True, attn_residual=True):
+    def __init__(self, cfg, num_tags, start_idx, stop_idx, device="cuda", inference=False, wgrad_overwrite=True, attn_residual=True,
+                 layers=(-1,), layer_mean=False):
         self.cfg, self.T, self.start, self.stop = cfg, num_tags, start_idx, stop_idx
         self.device = torch.device(device)
-        self.arena = Arena(tagger_specs(cfg, num_tags), self.device, with_grad=not inference)
+        # The hidden states the token feature is taken from (TransformerWordEmbeddings(layers=..., use_scalar_mix=...),
+        # flair/embeddings.py:2983-2991, 3315-3343): their first-sub-token rows side by side (W = k * H), or -- layer_mean, the
+        # reference's scalar mix, :3337 -- their mean (W = H).  The last layer alone is the path without any of this.
+        self.layer_sel = normalize_layers(layers, cfg.num_hidden_layers)
+        self.layer_mean = bool(layer_mean)
+        self.W = cfg.hidden_size if self.layer_mean else len(self.layer_sel) * cfg.hidden_size
+        if self.W > HEAD_MAX_WIDTH:
+            raise ValueError("a token feature of %d columns is wider than the emission head's %d" % (self.W, HEAD_MAX_WIDTH))
+        self._last_layer_only = self.layer_sel == (cfg.num_hidden_layers,)
+        self.arena = Arena(tagger_specs(cfg, num_tags, self.W), self.device, with_grad=not inference)
         # every weight gradient of the encoder is a tile of the grouped 256 x 256 launch (_wgrads): it may overwrite
         self.arena.wgrad_overwrite_ok = (not inference and cfg.hidden_size % 256 == 0 and cfg.intermediate_size % 256 == 0
                                          and bool(wgrad_overwrite))   # (False: zero them every step, the round-5 A/B)
@@ -541,8 +568,11 @@ class Tagger:
         self._enc_saved = (ids, pos_ids, maskbias, B, S, d_emb, d_layers) if need_grad else None
         return ac.x[L]
 
-    def encoder_backward(self, dx_top, grad_ready=None):
+    def encoder_backward(self, dx_top, grad_ready=None, inject=None):
         """dx_top bf16 [Mp,H] = d loss / d last hidden state; accumulates into arena.g.
+        inject: {i: [argument tuples of ops.scatter_add_rows_ld after its dst]} for hidden states i < L the loss also reads directly
+        (a layer selection): each is added to the gradient of x[i] -- layer i's QKV dgrad output, folded to bf16 for that -- before
+        layer i - 1 (i = 0: the embedding LayerNorm) takes it.
         grad_ready(lo, hi): called right after the launches that finalise arena.g[lo:hi] were enqueued -- the GEMM-weight
         gradients of a whole WGRAD_GROUP of layers (contiguous in the arena) -- so a data-parallel trainer can start that
         bucket's all-reduce while backward continues below (kbner.dp.GradReducer)."""
@@ -621,9 +651,14 @@ class Tagger:
             # QKV projection
             # (the next layer's LN2 backward folds this GEMM's slabs itself -- the first launch of that layer, before anything
             #  else writes the slab buffer; layer 0's gradient goes to the embedding LayerNorm as bf16)
-            dx_slabs = self._long_k_gemm(GEMM_NN, dqkv, a.bf(p + "qkv.weight"), Mp, H, 3 * H, ac.dx, ac, addend=dh1, finish=l == 0)
+            extra = inject.get(l) if inject else None
+            dx_slabs = self._long_k_gemm(GEMM_NN, dqkv, a.bf(p + "qkv.weight"), Mp, H, 3 * H, ac.dx, ac, addend=dh1,
+                                         finish=l == 0 or bool(extra))
             if dx_slabs is not None:
                 dx_slabs = (dx_slabs[0], dx_slabs[1], dh1)
+            if extra:     # ac.dx = d loss / d x[l] through the layers above; + what the head read of x[l] itself
+                for dout, col0, idx, n_, scale, de_, dl_ in extra:
+                    ops.scatter_add_rows_ld(dout, col0, idx, ac.dx, n_, scale, de_, dl_)
             # weight gradients dW += dY^T X are deferred and launched for WGRAD_GROUP layers at once
             # (no split-K, no atomics; the dY buffers rotate so they stay live until the group is flushed)
             pending += [(dhm, ac.act[l], H, F_, p + "ffn2.weight"), (dpre, ac.x1[l], F_, H, p + "ffn1.weight"),
@@ -675,13 +710,20 @@ class Tagger:
         sd = self._drop_rng.integers(0, 2 ** 32, size=2, dtype="uint64")
         return (int(sd[0]), ops.drop_thresh(self.head_dropout)), (int(sd[1]), ops.drop_thresh(self.locked_dropout))
 
-    def emissions(self, hidden, row_idx, B, n, drop=None):
+    def emissions(self, hidden, row_idx, B, n, drop=None, ac=None):
         """gather rows (first sub-token of each word token, -1 -> zeros) then the linear head.
-        -> (features f32 [B,n,T], pooled bf16 [B*n,H]).  drop (from _head_drop): the gather applies the head's element and locked
+        -> (features f32 [B,n,T], pooled bf16 [B*n,W]).  ac: the activation set of the forward that produced `hidden` -- with a layer
+        selection other than the last layer alone the rows come from its x[i] (one gather over all of them: concatenation or mean).
+        drop (from _head_drop): the gather applies the head's element and locked
         dropout in the reference's order -- element mask, word dropout (the -1 rows), locked mask -- and `pooled` is what the head
         read.  Under remove_x the reference masks all tokens and compacts afterwards; here the compacted rows are masked (row key =
         compacted row, sentence key = row // n): independent Bernoulli draws either way, the same distribution."""
-        if drop is None:
+        if not self._last_layer_only:
+            if ac is None:
+                raise ValueError("a layer selection needs the forward's activation set (emissions(..., ac=...))")
+            de, dl = drop if drop is not None else (ops.NO_DROP, ops.NO_DROP)
+            pooled = ops.gather_rows_layers([ac.x[i] for i in self.layer_sel], row_idx, n, mean=self.layer_mean, drop_e=de, drop_l=dl)
+        elif drop is None:
             pooled = ops.gather_rows(hidden, row_idx)
         else:
             pooled = ops.gather_rows_drop(hidden, row_idx, n, drop[0], drop[1])
@@ -729,7 +771,7 @@ class Tagger:
             cpos = batch["cpos"].long()
             crow_idx = torch.where(dropped[cpos.clamp(min=0)] & (cpos >= 0), torch.full_like(crow_idx, -1), crow_idx)
         drop = self._head_drop()
-        em, pooled = self.emissions(hidden, crow_idx, B, nc, drop)
+        em, pooled = self.emissions(hidden, crow_idx, B, nc, drop, ac=self.acts(R, S))
         return em, pooled, crow_idx, B, nc, R, S, drop
 
     def _backprop_emissions(self, demit, pooled, crow_idx, B, nc, R, S, grad_ready, l2=None, l2_scale=1.0, drop=None):
@@ -748,6 +790,22 @@ class Tagger:
             l2_val = part[0]
         ac = self.acts(R, S)
         ac.dx.zero_()
+        if not self._last_layer_only:
+            # dpooled [B*nc, W]: every selected hidden state gets its column block (the mean: the whole row / k) added to its
+            # gradient -- the last layer's right here, the others inside encoder_backward where their gradient exists.  The pass
+            # always starts at the top (dx_top = 0 when the last layer is not selected): no layer keeps a stale weight gradient.
+            L, H = self.cfg.num_hidden_layers, self.cfg.hidden_size
+            de, dl = drop if drop is not None else (ops.NO_DROP, ops.NO_DROP)
+            scale = 1.0 / len(self.layer_sel) if self.layer_mean else 1.0
+            inject = {}
+            for j, i in enumerate(self.layer_sel):
+                col0 = 0 if self.layer_mean else j * H
+                if i == L:
+                    ops.scatter_add_rows_ld(dpooled, col0, crow_idx, ac.dx, nc, scale, de, dl)
+                else:
+                    inject.setdefault(i, []).append((dpooled, col0, crow_idx, nc, scale, de, dl))
+            self.encoder_backward(ac.dx, grad_ready, inject=inject)
+            return l2_val
         if drop is None:
             ops.scatter_rows(dpooled, crow_idx, ac.dx)
         else:
@@ -770,7 +828,7 @@ class Tagger:
     def _forward_loss(self, batch, loss_scale, backward, weights, grad_ready=None):
         em, pooled, crow_idx, B, nc, R, S, drop = self._emit(batch)
         self.last_emissions = em   # f32 [B, nc, T] at the kept (non-S-X) tokens: the teacher view of multi-view training
-        self.last_pooled = pooled.view(B, nc, -1)   # bf16 [B, nc, H]: the same view's token representations (calculate_l2_loss)
+        self.last_pooled = pooled.view(B, nc, -1)   # bf16 [B, nc, W]: the same view's token representations (calculate_l2_loss)
         a = self.arena
         trans = a.param("transitions")
         w = self._sentence_weights(weights, B)
@@ -808,7 +866,7 @@ class Tagger:
           mode "posterior" (:2088-2101)  sum_b weights[b] * T^2 * sum_i KL(teacher || student tempered token marginals)
           mode "exact"     (:2049-2087)  sum_b weights[b] * max(0, -(E_teacher[path score / T] - logZ_T) T^2), the teacher being the
                                          context view's tempered pairwise posteriors under the shared transitions
-          teacher_pooled bf16[B,n_t,H]   calculate_l2_loss (:1988-1996,2026-2035): + sum_b weights[b] / H * |student token
+          teacher_pooled bf16[B,n_t,W]   calculate_l2_loss (:1988-1996,2026-2035): + sum_b weights[b] / W * |student token
                                          representations - the context view's|^2 at the real tokens; l2_only (:2038): only that
         (default weights 1/B = the reference's `.sum() / shape[0]`).  Returns a 0-d device tensor and, if `backward`, accumulates
         loss_scale * its gradient into arena.g."""
@@ -849,7 +907,7 @@ class Tagger:
         loss, demit = self.distill_terms(em, te, batch["clens"], w, tau, "none" if l2_only else mode, loss_scale, dtr)
         l2 = None
         if tp is not None:
-            H = pooled.shape[1]
+            H = pooled.shape[1]    # (the feature width W: the reference divides by the embedding length, :2033)
             if tp.shape[0] != B or tp.shape[1] < nc or tp.shape[2] != H:
                 raise ValueError("teacher token representations must be [B, >= %d, %d]" % (nc, H))
             valid = torch.arange(nc, device=self.device)[None, :] < batch["clens"][:, None]
@@ -894,7 +952,7 @@ class Tagger:
             dropped = torch.from_numpy(self._last_word_dropped).to(self.device).repeat(B)
             row_idx = torch.where(dropped, torch.full_like(row_idx, -1), row_idx)
         drop = self._head_drop()
-        em, pooled = self.emissions(hidden, row_idx, B, n, drop)
+        em, pooled = self.emissions(hidden, row_idx, B, n, drop, ac=self.acts(R, S))
         self.last_emissions = em
         loss, demit = self.kd_crf_terms(em, batch, kd, interpolation, tau, loss_scale, backward, weights)
         if backward:
@@ -973,7 +1031,7 @@ class Tagger:
         B, S = batch["B"], batch["S"]
         hidden = self.encoder_forward(batch["ids"], batch["pos_ids"], batch["maskbias"], batch.get("R", B), S, need_grad=False)
         n = batch["row_idx"].numel() // B
-        em, _ = self.emissions(hidden, batch["row_idx"], B, n)
+        em, _ = self.emissions(hidden, batch["row_idx"], B, n, ac=self.acts(batch.get("R", B), S))
         return em
 
     def viterbi(self, emissions, lens):

@@ -317,6 +317,53 @@ def scatter_rows_drop(dout, idx, dsrc, n, drop_e=NO_DROP, drop_l=NO_DROP):
     L.call("kbner_scatter_rows_drop", ptr(dout), ptr(idx), ptr(dsrc), R, H, n, se, te, sl, tl, stream_ptr())
 
 
+def gather_rows_layers(srcs, idx, n, mean=False, drop_e=NO_DROP, drop_l=NO_DROP, out=None):
+    """The token features of an encoder layer selection: srcs = k bf16 [*, H] hidden states (1 <= k <= 32), idx i32 [B * n] (-1 ->
+    zero row).  mean=False: the k selected rows side by side, bf16 [R, k * H] (k * H <= 8192); mean=True: their mean, bf16 [R, H].
+    drop_e / drop_l: the head's element / locked dropout sites as for gather_rows_drop, keyed by the column of the output row."""
+    srcs = list(srcs)
+    k = len(srcs)
+    _chk(idx, I32, "idx")
+    if not 1 <= k <= 32:
+        raise L.KbnerError("gather_rows_layers: 1 to 32 source matrices (got %d)" % k)
+    H = srcs[0].shape[-1]
+    for s_ in srcs:
+        _chk(s_, BF16, "srcs[i]")
+        if s_.dim() != 2 or s_.shape[-1] != H:
+            raise L.KbnerError("gather_rows_layers: every source is bf16 [*, %d]" % H)
+    R, W = idx.numel(), (H if mean else k * H)
+    n = int(n)
+    if H % 8 or n < 1 or R % n or (not mean and W > 8192):
+        raise L.KbnerError("gather_rows_layers: H %% 8 == 0, idx [B * n] with n >= 1, a concatenation of at most 8192 columns")
+    if out is None:
+        out = torch.empty((R, W), dtype=BF16, device=srcs[0].device)
+    else:
+        _chk(out, BF16, "out")
+        if out.dim() != 2 or out.shape[0] < R or out.shape[1] != W:
+            raise L.KbnerError("gather_rows_layers: out must be bf16 [>= %d, %d]" % (R, W))
+    (se, te), (sl, tl) = drop_e, drop_l
+    ptrs = (ctypes.c_void_p * k)(*[s_.data_ptr() for s_ in srcs])
+    L.call("kbner_gather_rows_layers", ptrs, k, 1 if mean else 0, ptr(idx), ptr(out), R, H, n, int(se) & 0xFFFFFFFF, int(te),
+           int(sl) & 0xFFFFFFFF, int(tl), stream_ptr())
+    return out
+
+
+def scatter_add_rows_ld(dout, col0, idx, dst, n, scale=1.0, drop_e=NO_DROP, drop_l=NO_DROP):
+    """its backward for one source: dst[idx[r], :] += dout[r, col0:col0 + H] * m[r, col0:col0 + H] * scale for idx[r] >= 0 (unique
+    indices; other rows untouched).  dout bf16 [R, ld], dst bf16 [*, H]; the masks are keyed by the column of the ld-wide row."""
+    _chk(dout, BF16, "dout"); _chk(idx, I32, "idx"); _chk(dst, BF16, "dst")
+    R, n, col0 = idx.numel(), int(n), int(col0)
+    if dout.dim() != 2 or dst.dim() != 2 or dout.shape[0] < R:
+        raise L.KbnerError("scatter_add_rows_ld: dout bf16 [>= R, ld], dst bf16 [*, H]")
+    ld, H = dout.shape[1], dst.shape[1]
+    if ld % 8 or H % 8 or col0 % 8 or col0 < 0 or col0 + H > ld or n < 1 or R % n:
+        raise L.KbnerError("scatter_add_rows_ld: ld, H, col0 multiples of 8 with col0 + H <= ld, idx [B * n] with n >= 1")
+    (se, te), (sl, tl) = drop_e, drop_l
+    L.call("kbner_scatter_add_rows_ld", ptr(dout), ld, col0, ptr(idx), ptr(dst), R, H, float(scale), n, int(se) & 0xFFFFFFFF, int(te),
+           int(sl) & 0xFFFFFFFF, int(tl), stream_ptr())
+    return dst
+
+
 def head_fwd(x, w, bias):
     _chk(x, BF16, "x"); _chk(w, F32, "w"); _chk(bias, F32, "bias")
     R, H = x.shape
