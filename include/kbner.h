@@ -351,6 +351,32 @@ int kbner_attn_fwd(const kbner_bf16* qkv, const float* maskbias, kbner_bf16* ctx
 int kbner_attn_bwd(const kbner_bf16* qkv, const kbner_bf16* ctx, const uint8_t* ctx_lo, const kbner_bf16* dctx,
                    const float* maskbias, const float* lse, float* Dws, kbner_bf16* dqkv, int B, int S, int H, int A,
                    uint32_t drop_seed, uint32_t drop_thresh, float* dbias_qkv, void* stream);
+/* The same attention for FEW queries per sentence against ALL its keys (csrc/attn_rows.hip): the last encoder layer, of which the
+ * tagger head reads the first sub-token of each kept word only.  q_pos i32 [B, nq] (nq >= 1): the queries' positions inside their
+ * sentence, unique per sentence, in any order; < 0 (or >= S) = no query.  Same constraints on S, H, A, same scores, softmax and
+ * dropout keys (the ORIGINAL query / key indices of the head) as kbner_attn_fwd / _bwd; qkv / dqkv are the full [>= B*S, 3H].
+ *   fwd: ctx_c bf16 [B*nq, H] and o32 f32 [B*nq, H] = the context rows in list order (zero rows for "no query"),
+ *        lse_c f32 [B, A, nq] the log-sum-exp of the undropped softmax
+ *   bwd: dctx_c bf16 [B*nq, H] = dO at the listed queries -> EVERY row [0, B*S) of dqkv: dK | dV of all keys, dQ at the listed
+ *        rows, exact zeros in the Q third of all others; D = rowdot(dO, O) from o32 as kbner_attn_bwd sees O (its bf16 rounding
+ *        plus the e5m2 byte of the residual, formed on the fly), and the probabilities in the arithmetic of the kbner_attn_fwd /
+ *        _bwd kernels that would run the shape: the two paths round the same values and differ by summation order only;
+ *        dbias_qkv f32[3H] (nullable) += column sums of dqkv */
+int kbner_attn_rows_fwd(const kbner_bf16* qkv, const float* maskbias, const int* q_pos, kbner_bf16* ctx_c, float* o32, float* lse_c,
+                        int B, int S, int H, int A, int nq, uint32_t drop_seed, uint32_t drop_thresh, void* stream);
+int kbner_attn_rows_bwd(const kbner_bf16* qkv, const int* q_pos, const kbner_bf16* dctx_c, const float* o32, const float* lse_c,
+                        const float* maskbias, kbner_bf16* dqkv, int B, int S, int H, int A, int nq, uint32_t drop_seed,
+                        uint32_t drop_thresh, float* dbias_qkv, void* stream);
+/* Hidden dropout on compact rows: row r of y stands for row row_ids[r] (< 0: no mask) of the full [tokens, H] hidden state and draws
+ * that row's bits of the site -- element (row_ids[r], c), what the GEMM epilogue and kbner_ln_bwd draw in the full path:
+ *   out[r,c] = bf16( keep ? (y[r,c] + bias[c]) / (1-p) : 0  (+ addend[r,c]) )      y f32 (y_is_f32) or bf16 [R, H]; bias, addend nullable */
+int kbner_rows_drop_add(const void* y, int y_is_f32, const float* bias, const kbner_bf16* addend, const int* row_ids, kbner_bf16* out,
+                        int R, int H, uint32_t drop_seed, uint32_t drop_thresh, void* stream);
+/* kbner_ln_bwd for such compact rows: dhm and the bias gradient draw the mask bits of row row_ids[r] (from the fp32 dh, as the
+ * full path does -- no second rounding); everything else is kbner_ln_bwd's */
+int kbner_ln_bwd_rows(const kbner_bf16* dy, const kbner_bf16* h, const float* mean, const float* rstd, const float* gamma,
+                      kbner_bf16* dh, float* dgamma, float* dbeta, float* dbias, float* ws, int M, int H, kbner_bf16* dhm,
+                      const int* row_ids, uint32_t drop_seed, uint32_t drop_thresh, void* stream);
 
 /* ---------------- LSTM recurrence (inference): BiLSTM tagger head + FlairEmbeddings character LMs ---------------- */
 /* One time step of torch.nn.LSTM's recurrent half for a whole batch and `ndir` directions / models

@@ -352,7 +352,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
       }
     if (dh) store_row_bf16<NCH>(dh + (size_t)r * H, H, lane, d);
     if (!EMBED && drop_thresh) {
-      drop_row<NCH>(d, ck, drop_seed, drop_thresh, dscale, r);
+      // (not EMBED: `ids`, when given, names the row whose mask bits row r draws -- compact rows, kbner_ln_bwd_rows)
+      drop_row<NCH>(d, ck, drop_seed, drop_thresh, dscale, ids != nullptr ? ids[r] : r);
       store_row_bf16<NCH>(dhm + (size_t)r * H, H, lane, d);
     }
 #pragma unroll
@@ -535,6 +536,16 @@ int kbner_ln_bwd(const bf16_t* dy, const bf16_t* h, const float* mean, const flo
   KBNER_CHECK_ARG(drop_thresh == 0 || dhm != nullptr);
   return ln_bwd_launch<false, false>(dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias, nullptr, nullptr, nullptr, nullptr, ws, M, H, dhm,
                                      drop_seed, drop_thresh, nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+// kbner_ln_bwd on COMPACT rows: row r stands for row row_ids[r] of the full hidden state and draws that row's mask bits for dhm
+// and the bias gradient (the last encoder layer computed on the tagger head's rows only); everything else is kbner_ln_bwd
+int kbner_ln_bwd_rows(const bf16_t* dy, const bf16_t* h, const float* mean, const float* rstd, const float* gamma, bf16_t* dh,
+                      float* dgamma, float* dbeta, float* dbias, float* ws, int M, int H, bf16_t* dhm, const int* row_ids,
+                      uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
+  KBNER_CHECK_ARG(row_ids != nullptr && (drop_thresh == 0 || dhm != nullptr));
+  return ln_bwd_launch<false, false>(dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias, row_ids, nullptr, nullptr, nullptr, ws, M, H,
+                                     dhm, drop_seed, drop_thresh, nullptr, 0, nullptr, 0, nullptr, stream);
 }
 
 // kbner_ln_fwd / kbner_ln_bwd with the input row folded from split-K slabs (ws f32 [splits][M, H]) instead of read as bf16: what

@@ -794,6 +794,61 @@ extern "C" int kbner_splitk_finish(const float* ws, int splits, const float* bia
   KBNER_LAUNCH_RET();
 }
 
+// Hidden dropout on COMPACT rows (the last encoder layer computed at the tagger head's rows only): row r of y stands for row
+// row_ids[r] of the full [tokens, H] hidden state, and draws that row's mask -- the bits the GEMM epilogue / kbner_ln_bwd draw
+// for it in the full path:
+//     out[r,:] = bf16( keep(row_ids[r], c) ? (y[r,c] + bias[c]) / (1-p) : 0  (+ addend[r,c]) )
+// y is fp32 (the compact GEMM's fp32 output, so the value is rounded once, as in the fused epilogue) or bf16.  The backward of
+// these sites is kbner_ln_bwd_rows (csrc/layernorm.hip), which masks the fp32 dh.  8 columns per thread.
+template <typename TY>
+__global__ __launch_bounds__(256) void rows_drop_add_kernel(const TY* __restrict__ y, const float* __restrict__ bias,
+                                                            const bf16_t* __restrict__ addend, const int* __restrict__ row_ids,
+                                                            bf16_t* __restrict__ out, int R, int H, uint32_t seed, uint32_t thresh) {
+  const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (i >= (size_t)R * H) return;
+  const int r = (int)(i / H), c = (int)(i % H);
+  float v[8];
+  if constexpr (sizeof(TY) == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(y + i), b = *reinterpret_cast<const float4*>(y + i + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+    unpack8bf(*reinterpret_cast<const uint4*>(y + i), v);
+  }
+  if (bias) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += bias[c + j];
+  }
+  const int row = row_ids[r];
+  if (thresh && row >= 0) {
+    const uint32_t rk = drop_rowkey(seed, (uint32_t)row);
+    const float ds = drop_scale(thresh);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = drop_keep(rk, drop_colkey(seed, (uint32_t)(c + j)), thresh) ? v[j] * ds : 0.0f;
+  }
+  if (addend) {
+    float a[8];
+    unpack8bf(*reinterpret_cast<const uint4*>(addend + i), a);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += a[j];
+  }
+  *reinterpret_cast<uint4*>(out + i) = pack8bf(v);
+}
+
+extern "C" int kbner_rows_drop_add(const void* y, int y_is_f32, const float* bias, const bf16_t* addend, const int* row_ids, bf16_t* out,
+                                   int R, int H, uint32_t drop_seed, uint32_t drop_thresh, void* stream) {
+  KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0);
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(y != nullptr && row_ids != nullptr && out != nullptr);
+  if (y_is_f32)
+    FLAT_LAUNCH(rows_drop_add_kernel<float>, (size_t)R * H / 8, stream, static_cast<const float*>(y), bias, addend, row_ids, out, R, H,
+                drop_seed, drop_thresh);
+  else
+    FLAT_LAUNCH(rows_drop_add_kernel<bf16_t>, (size_t)R * H / 8, stream, static_cast<const bf16_t*>(y), bias, addend, row_ids, out, R, H,
+                drop_seed, drop_thresh);
+  KBNER_LAUNCH_RET();
+}
+
 // ---- the rest
 
 // Multi-view training's representation term (FastSequenceTagger._calculate_multi_view_loss with calculate_l2_loss,

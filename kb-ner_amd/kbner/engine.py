@@ -262,12 +262,83 @@ class _Acts:
         self.defer_ln_ws = None     # small batches: one partial-sum workspace per LayerNorm / per FFN-up bias (Tagger.encoder_backward)
         self.colsum_ws_all = None
 
+        self.rows = None            # _RowActs: the last layer on the tagger head's rows only (Tagger.HEAD_ROWS_ONLY), first use
+        self._rows_counted = 0      # bytes of it that self.nbytes holds
+        self.dh1_full = None        # bf16 [Mp, H], zero but for the rows a head-rows backward is using (Tagger._last_layer_rows_backward)
+        self.dh1_rows = None        # ... those rows (i32), while they are set
+
+    def head_rows(self, cfg, nc, dropping=False):
+        """the compact activation set, viewed at nc kept tokens per sentence.  ONE set per (B, S) shape, sized for the most rows the
+        path takes (4 * nc <= S): a batch with another nc re-uses it through a view, nothing is re-allocated or re-filled."""
+        if self.rows is None:
+            self.rows = _RowActs(cfg, self.B, self.S, _round_up(self.B * (self.S // 4), 256), self._z, self.h0.device)
+            self.dh1_full = self._z(self.Mp, self._H)
+        if dropping:
+            self.rows.drop_buffers()
+        counted = self.rows.nbytes + 2 * self.Mp * self._H
+        self.nbytes = getattr(self, "nbytes", 0) + counted - self._rows_counted
+        self._rows_counted = counted
+        return self.rows.at(_round_up(self.B * nc, 256))
+
     def drop_buffers(self):
         """masked copies of dh / dh1 (the dY of the two GEMMs whose outputs were dropped); allocated on first training use"""
         if self.dhm is None:
             self.dhm = [self._z(self.Mp, self._H) for _ in range(WGRAD_GROUP)]
             self.dh1m = [self._z(self.Mp, self._H) for _ in range(WGRAD_GROUP)]
         return self.dhm, self.dh1m
+
+
+class _RowActs:
+    """Activations and backward workspaces of the LAST encoder layer computed on the tagger head's rows only (Tagger.HEAD_ROWS_ONLY),
+    `cap` rows of each; a step works on the leading Mc = B * nc rounded up to 256 of them (at(Mc)): row r < B * nc stands for encoder
+    row row_ids[r] (the first sub-token of a kept word; -1: none), the rest is padding.  Zero-filled, never torch.empty: pad rows
+    and -1 rows enter weight-gradient products and column sums (their dY rows are exact zeros, so whatever finite value the forward
+    leaves in them contributes nothing)."""
+
+    def __init__(self, cfg, B, S, cap, z, device):
+        H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        self.cap = cap
+        self.row_ids = torch.full((cap,), -1, dtype=I32, device=device)
+        self.ctx, self.o32, self.lse = z(cap, H), z(cap, H, dt=F32), z(A * cap, dt=F32)
+        self.xres, self.h1, self.x1, self.h2, self.xo = (z(cap, H) for _ in range(5))
+        self.act, self.dact = z(cap, F_), z(cap, F_)
+        self.st1a, self.st1b, self.st2a, self.st2b = (z(cap, dt=F32) for _ in range(4))
+        self.dx, self.dh, self.dx1, self.dh1, self.dctx, self.zeros = (z(cap, H) for _ in range(6))
+        self.dpre = z(cap, F_)
+        self.y32 = self.dhm = self.dh1m = None   # hidden dropout: fp32 GEMM output, masked dY copies (first training use)
+        self._z, self._H = z, H
+        self._views = {}
+        self.last_n = -1     # B * nc of the last step that used the set
+        self.nbytes = 2 * cap * (15 * H + 3 * F_) + 4 * cap * H + 4 * A * cap
+
+    def drop_buffers(self):
+        if self.y32 is None:
+            self.y32 = self._z(self.cap, self._H, dt=F32)
+            self.dhm, self.dh1m = self._z(self.cap, self._H), self._z(self.cap, self._H)
+            self.nbytes += 8 * self.cap * self._H
+
+    def at(self, Mc):
+        v = self._views.get(Mc)
+        if v is None:
+            v = self._views[Mc] = _RowView(self, Mc)
+        return v
+
+
+class _RowView:
+    """the leading Mc rows of a _RowActs (every buffer sliced on first use), plus what belongs to that row count alone"""
+
+    def __init__(self, acts, Mc):
+        assert Mc <= acts.cap
+        self._acts, self.Mc, self.n_used, self.sent_base = acts, Mc, -1, None
+        self.splitk_ws = self.colsum_ws = None     # (_long_k_gemm's slabs, the FFN-down dgrad's column-sum lines: sized by Mc)
+
+    def __getattr__(self, name):     # (only reached for names not set yet)
+        t = getattr(self._acts, name)
+        if t is None:
+            return None
+        v = t if name == "lse" else t[:self.Mc]
+        setattr(self, name, v)
+        return v
 
 
 WGRAD_GROUP = 4
@@ -305,8 +376,11 @@ class Tagger:
     forward_loss / _calculate_loss (flair/models/sequence_tagger_model.py:844,1899,2426)."""
 
     def __init__(self, cfg, num_tags, start_idx, stop_idx, device="cuda", inference=False, wgrad_overwrite=True, attn_residual=True,
-                 layers=(-1,), layer_mean=False):
+                 layers=(-1,), layer_mean=False, head_rows_only=True):
         self.cfg, self.T, self.start, self.stop = cfg, num_tags, start_idx, stop_idx
+        self.HEAD_ROWS_ONLY = bool(head_rows_only)   # (False: the last layer on every row, the A/B; see the class default)
+        self.last_path = None            # "head_rows" | "full": which of the two the last _emit took
+        self._rows_saved = None
         self.device = torch.device(device)
         # The hidden states the token feature is taken from (TransformerWordEmbeddings(layers=..., use_scalar_mix=...),
         # flair/embeddings.py:2983-2991, 3315-3343): their first-sub-token rows side by side (W = k * H), or -- layer_mean, the
@@ -424,6 +498,14 @@ class Tagger:
     # correction D from the pair: include/kbner.h kbner_attn_bwd.  Class default of the constructor's attn_residual; without it a query.weight
     # gradient is 16 % off at L = 24, so tests/test_abi_cpu.py pins the default.
     ATTN_RESIDUAL = True
+    # The tagger head reads the last hidden state at the first sub-token of each kept word only (a short sentence followed by up to
+    # 512 sub-tokens of context that remove_x drops: 16 of 512 rows in the benchmark).  Layers 0 .. L-2 need every row -- the next
+    # layer's keys and values -- the LAST layer does not: behind its (full) QKV projection it runs on the head's rows alone -- the
+    # few-query attention kernels of csrc/attn_rows.hip, then output projection, LN1, FFN and LN2 on B * nc rows padded to 256 --
+    # and its backward hands a full dqkv back to the common loop.  Taken by _emit / _backprop_emissions when the token feature is the
+    # last layer alone, the batch has no sliding windows (R == B) and 4 * nc <= S; otherwise, and for every other caller of the
+    # encoder, the full path runs.  Class default of the constructor's head_rows_only.
+    HEAD_ROWS_ONLY = True
     ACTS_BUDGET_BYTES = 120 << 30  # resident activation sets (one per (B, S) shape), least-recently-used first out
 
     def acts(self, B, S):
@@ -448,13 +530,16 @@ class Tagger:
     FUSE_SPLITK_LN = True  # the LayerNorm behind a split-K GEMM folds the fp32 slabs itself (no kbner_splitk_finish launch)
     DEFER_REDUCE_MAX_TOKENS = 16384  # micro-batches up to this many (padded) sub-tokens batch their column-sum reductions (encoder_backward)
 
-    def _long_k_gemm(self, layout, A, W, Mp, N, K, C, ac, bias=None, addend=None, drop=ops.NO_DROP, finish=True):
+    def _long_k_gemm(self, layout, A, W, Mp, N, K, C, ac, bias=None, addend=None, drop=ops.NO_DROP, finish=True, split_as=None):
         """C = bf16(dropout(A.W + bias) + addend) for the three K >= 3H GEMMs of a layer (FFN-down forward, its two dgrad
         siblings).  With a small micro-batch the [Mp, H] output has a few dozen tiles, each a serial chain of K/64 DMA
         round trips (86 us at K=4096 whatever Mp): K is then cut over up to 4 workgroups per tile (ops.gemm_splitk)."""
         tiles = (Mp // 256) * (N // 256) if Mp % 256 == 0 and N % 256 == 0 else 0
+        # split_as (the last layer's compact rows): K is cut exactly where the same GEMM over that many rows would cut it, so a
+        # compact row is summed in the order its row of the full GEMM is
+        ref_tiles = tiles if split_as is None else ((split_as // 256) * (N // 256) if split_as % 256 == 0 and N % 256 == 0 else 0)
         splits = 0
-        if 0 < tiles <= self.SPLITK_MAX_TILES and not ops.FORCE_128:
+        if tiles > 0 and 0 < ref_tiles <= self.SPLITK_MAX_TILES and not ops.FORCE_128:
             for sp in (4, 3, 2):
                 if K % (64 * sp) == 0 and K // sp >= 512:
                     splits = sp
@@ -468,7 +553,9 @@ class Tagger:
                 return ac.splitk_ws, splits      # the LayerNorm that consumes C folds the slabs itself (C is NOT written)
         else:
             epi = (EPI_BIAS if bias is not None else 0) | (EPI_ADD if addend is not None else 0)
-            ops.gemm(layout, A, W, Mp, N, K, C=C, bias=bias, addend=addend, epi=epi, drop=drop, occupancy=True)
+            # (compact rows run on the kernel the same GEMM over split_as rows runs on: the same sums in the same order)
+            ops.gemm(layout, A, W, Mp, N, K, C=C, bias=bias, addend=addend, epi=epi, drop=drop,
+                     occupancy=split_as is None or not ops.uses_256(split_as, N, occupancy=True))
 
     # ---------------------------------------------------------------- encoder
     # Forward-only passes (evaluate, predict, the frozen encoders of a stack) are ~170 launches of ~50 us of Python + ctypes each:
@@ -527,16 +614,19 @@ class Tagger:
         st["graph"].replay()
         return st["out"]
 
-    def _encoder_forward(self, ids, pos_ids, maskbias, B, S, need_grad=True):
+    def _encoder_forward(self, ids, pos_ids, maskbias, B, S, need_grad=True, seeds=None, head_rows=None):
         """ids/pos_ids i32[Mp], maskbias f32[B,S] -> last hidden state bf16 [Mp,H] (rows >= B*S are padding).
         need_grad=False (inference: evaluate, the frozen encoders of an embedding stack) runs the FFN-up epilogue without the
-        gelu' output that only encoder_backward reads; a backward after such a forward fails loudly."""
+        gelu' output that only encoder_backward reads; a backward after such a forward fails loudly.
+        seeds: this forward's _site_seeds() when the caller has drawn them already.  head_rows = (row_idx i32[B*nc], nc): the last
+        layer runs on these rows only (_last_layer_rows_forward) -- of the returned hidden state only they are written."""
         cfg, a = self.cfg, self.arena
         H, F_, A, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
         ac = self.acts(B, S)
         Mp = ac.Mp
         eps = cfg.layer_norm_eps
-        d_emb, d_layers = self._site_seeds()
+        d_emb, d_layers = self._site_seeds() if seeds is None else seeds
+        self._rows_saved = None
         a.catch_up_rows(ids)   # FusedAdamW.lazy_rows: the looked-up rows owe the zero-gradient steps since they were last touched
         ops.embed_ln_fwd(ids, pos_ids, a.param("emb.word"), a.param("emb.pos"), a.param("emb.type")[0], a.param("emb.ln.g"),
                          a.param("emb.ln.b"), eps, ac.h0, ac.x[0], ac.emb_mean, ac.emb_rstd, drop=d_emb)
@@ -545,6 +635,9 @@ class Tagger:
             x = ac.x[l]
             d_att, d_o, d_f = d_layers[l]
             ops.gemm(GEMM_NT, x, a.bf(p + "qkv.weight"), Mp, 3 * H, H, C=ac.qkv[l], bias=a.param(p + "qkv.bias"), epi=EPI_BIAS, occupancy=True)
+            if head_rows is not None and l == L - 1:
+                self._last_layer_rows_forward(ac, l, maskbias, d_layers[l], head_rows[0], head_rows[1])
+                break
             if need_grad and self.ATTN_RESIDUAL and ac.ctx_lo[l] is None:
                 ac.ctx_lo[l] = torch.empty((Mp * H,), dtype=torch.uint8, device=self.device)   # what the backward reads is written
             ops.attn_fwd(ac.qkv[l], maskbias, ac.ctx[l], ac.lse[l], B, S, H, A, drop=d_att,
@@ -568,6 +661,111 @@ class Tagger:
         self._enc_saved = (ids, pos_ids, maskbias, B, S, d_emb, d_layers) if need_grad else None
         return ac.x[L]
 
+    # ---------------------------------------------------------------- the last layer on the head's rows (HEAD_ROWS_ONLY)
+    def _last_layer_rows_forward(self, ac, l, maskbias, drops, row_idx, nc):
+        """Layer l behind its QKV projection, for the encoder rows row_idx i32[B*nc] (-1: none) only: few-query attention against
+        the full K / V, then output projection, LN1, FFN and LN2 on the compact rows.  The results are scattered into ac.x[l + 1] at
+        their rows, where the head's gather finds them; everything the backward needs stays in ac.rows.
+        Hidden dropout draws the bits of the ORIGINAL rows: the compact GEMM leaves fp32, kbner_rows_drop_add applies bias, mask and
+        residual with one rounding, as the fused epilogue of the full path does."""
+        cfg, a = self.cfg, self.arena
+        H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        B, S, eps, p = ac.B, ac.S, cfg.layer_norm_eps, "l%d." % l
+        d_att, d_o, d_f = drops
+        rw = ac.head_rows(cfg, nc, dropping=bool(d_o[1] or d_f[1]))
+        Mc, n = rw.Mc, B * nc
+        # every compact GEMM runs on the kernel (256- or 128-row tiles) its full counterpart runs on: a row's sum is the same
+        occ = lambda N: not ops.uses_256(ac.Mp, N, occupancy=True)  # noqa: E731
+        if rw.n_used != n:     # (per view: the sentence offsets of this row count)
+            rw.sent_base = (torch.arange(n, dtype=I32, device=self.device) // nc) * S
+            rw.n_used = n
+        if ac.rows.last_n != n:     # another nc than the last step's: rows that were real may now be padding
+            rw.ctx.zero_()
+            ac.rows.row_ids.fill_(-1)
+            ac.rows.last_n = n
+        rw.row_ids[:n].copy_(row_idx)
+        q_pos = torch.where(row_idx >= 0, row_idx - rw.sent_base, row_idx).contiguous()
+        ops.attn_rows_fwd(ac.qkv[l], maskbias, q_pos, rw.ctx, rw.o32, rw.lse, B, S, H, A, drop=d_att)
+        ops.gather_rows(ac.x[l], rw.row_ids, out=rw.xres)
+        if d_o[1]:
+            self._gemm_nt_f32(rw.ctx, a.bf(p + "o.weight"), Mc, H, H, rw.y32, occ(H))
+            ops.rows_drop_add(rw.y32, rw.row_ids, rw.h1, d_o, bias=a.param(p + "o.bias"), addend=rw.xres)
+        else:
+            ops.gemm(GEMM_NT, rw.ctx, a.bf(p + "o.weight"), Mc, H, H, C=rw.h1, bias=a.param(p + "o.bias"), addend=rw.xres,
+                     epi=EPI_BIAS | EPI_ADD, occupancy=occ(H))
+        ops.ln_fwd(rw.h1, a.param(p + "ln1.g"), a.param(p + "ln1.b"), eps, rw.x1, rw.st1a, rw.st1b)
+        ops.gemm(GEMM_NT, rw.x1, a.bf(p + "ffn1.weight"), Mc, F_, H, C=rw.act, out2=rw.dact, bias=a.param(p + "ffn1.bias"),
+                 epi=EPI_BIAS | EPI_GELU, occupancy=occ(F_))
+        slabs = None
+        if d_f[1]:
+            self._gemm_nt_f32(rw.act, a.bf(p + "ffn2.weight"), Mc, H, F_, rw.y32, occ(H))
+            ops.rows_drop_add(rw.y32, rw.row_ids, rw.h2, d_f, bias=a.param(p + "ffn2.bias"), addend=rw.x1)
+        else:
+            slabs = self._long_k_gemm(GEMM_NT, rw.act, a.bf(p + "ffn2.weight"), Mc, H, F_, rw.h2, rw, bias=a.param(p + "ffn2.bias"),
+                                      addend=rw.x1, finish=False, split_as=ac.Mp)
+        if slabs is not None:
+            ops.ln_fwd_slabs(slabs[0], slabs[1], a.param(p + "ffn2.bias"), rw.x1, ops.NO_DROP, rw.h2, a.param(p + "ln2.g"),
+                             a.param(p + "ln2.b"), eps, rw.xo, rw.st2a, rw.st2b)
+        else:
+            ops.ln_fwd(rw.h2, a.param(p + "ln2.g"), a.param(p + "ln2.b"), eps, rw.xo, rw.st2a, rw.st2b)
+        ops.scatter_rows(rw.xo, rw.row_ids, ac.x[l + 1])
+        self._rows_saved = (rw, q_pos, nc)
+
+    @staticmethod
+    def _clear_dh1_rows(ac):
+        """the rows of ac.dh1_full a head-rows backward set, back to zero"""
+        if ac.dh1_rows is not None:
+            ops.scatter_rows(ac.rows.zeros[:ac.dh1_rows.numel()], ac.dh1_rows, ac.dh1_full)
+            ac.dh1_rows = None
+
+    @staticmethod
+    def _gemm_nt_f32(A, W, M, N, K, y32, occupancy):
+        """y32 f32[M, N] = A . W^T, unrounded: plain fp32 stores on the 256-row kernel, zero + fp32 adds on the 128-row one"""
+        if ops.uses_256(M, N, occupancy=occupancy):
+            ops.gemm(GEMM_NT, A, W, M, N, K, C32=y32, epi=EPI_STORE32, occupancy=occupancy)
+        else:
+            y32.zero_()
+            ops.gemm(GEMM_NT, A, W, M, N, K, C32=y32, epi=EPI_ATOMIC32, occupancy=occupancy)
+
+    def _last_layer_rows_backward(self, ac, l, maskbias, drops, dqkv):
+        """backward of _last_layer_rows_forward from rw.dx (d loss / d the compact output rows; -1 and pad rows zero): the bias,
+        gamma and beta gradients into arena.g, the full dqkv of the layer, and -> (dh1 scattered to its encoder rows in an otherwise
+        zero [Mp, H] buffer: the residual gradient into x[l], the three compact weight-gradient problems for _wgrads)."""
+        cfg, a = self.cfg, self.arena
+        H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        B, S, p = ac.B, ac.S, "l%d." % l
+        d_att, d_o, d_f = drops
+        rw, q_pos, _ = self._rows_saved
+        Mc = rw.Mc
+        occ = lambda N: not ops.uses_256(ac.Mp, N, occupancy=True)  # noqa: E731  (as in the forward)
+        dhm = rw.dhm if d_f[1] else rw.dh
+        dh1m = rw.dh1m if d_o[1] else rw.dh1
+        self._clear_dh1_rows(ac)   # (only after a backward pass that did not reach its end)
+        # LN2 backward (fused: d ffn2.bias); with hidden dropout dhm = mask * dh draws the mask bits of the ORIGINAL rows
+        ops.ln_bwd(rw.dx, rw.h2, rw.st2a, rw.st2b, a.param(p + "ln2.g"), rw.dh, a.grad(p + "ln2.g"), a.grad(p + "ln2.b"),
+                   a.grad(p + "ffn2.bias"), dhm=dhm if d_f[1] else None, drop=d_f, row_ids=rw.row_ids if d_f[1] else None)
+        if ops.uses_256(Mc, F_, occupancy=occ(F_)):
+            if rw.colsum_ws is None:
+                rw.colsum_ws = torch.empty((2 * (Mc // 128), F_), dtype=F32, device=self.device)
+            trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mc, F_, H, C=rw.dpre, aux=rw.dact,
+                             epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=rw.colsum_ws, occupancy=occ(F_))
+            ops.colsum_rows_f32(rw.colsum_ws, 2 * (Mc // trows), a.grad(p + "ffn1.bias"))
+        else:
+            ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mc, F_, H, C=rw.dpre, aux=rw.dact, epi=EPI_DGELU, occupancy=occ(F_))
+            ops.colsum(rw.dpre, a.grad(p + "ffn1.bias"))
+        # (the row-keyed LayerNorm backward reads a bf16 dy: with dropout a split-K GEMM folds its slabs itself)
+        slabs = self._long_k_gemm(GEMM_NN, rw.dpre, a.bf(p + "ffn1.weight"), Mc, H, F_, rw.dx1, rw, addend=rw.dh, finish=bool(d_o[1]), split_as=ac.Mp)
+        if slabs is not None:
+            slabs = (slabs[0], slabs[1], rw.dh)
+        ops.ln_bwd(rw.dx1, rw.h1, rw.st1a, rw.st1b, a.param(p + "ln1.g"), rw.dh1, a.grad(p + "ln1.g"), a.grad(p + "ln1.b"),
+                   a.grad(p + "o.bias"), dhm=dh1m if d_o[1] else None, drop=d_o, dy_slabs=slabs, row_ids=rw.row_ids if d_o[1] else None)
+        ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), Mc, H, H, C=rw.dctx, occupancy=occ(H))
+        ops.attn_rows_bwd(ac.qkv[l], q_pos, rw.dctx, rw.o32, rw.lse, maskbias, dqkv, B, S, H, A, drop=d_att, dbias=a.grad(p + "qkv.bias"))
+        ac.dh1_rows = rw.row_ids.clone()     # (zeroed again at the end of the pass -- or, had it not got there, below)
+        ops.scatter_rows(rw.dh1, ac.dh1_rows, ac.dh1_full)
+        return ac.dh1_full, [(dhm, rw.act, H, F_, p + "ffn2.weight", Mc), (rw.dpre, rw.x1, F_, H, p + "ffn1.weight", Mc),
+                             (dh1m, rw.ctx, H, H, p + "o.weight", Mc)]
+
     def encoder_backward(self, dx_top, grad_ready=None, inject=None):
         """dx_top bf16 [Mp,H] = d loss / d last hidden state; accumulates into arena.g.
         inject: {i: [argument tuples of ops.scatter_add_rows_ld after its dst]} for hidden states i < L the loss also reads directly
@@ -583,6 +781,11 @@ class Tagger:
         ids, pos_ids, maskbias, B, S, d_emb, d_layers = self._enc_saved
         ac = self.acts(B, S)
         Mp = ac.Mp
+        # the forward ran its last layer on the head's rows only (_emit): of dx_top exactly those rows carry a gradient (the scatter
+        # of _backprop_emissions skips the -1 entries, whose compact rows therefore come out zero, like the padding's)
+        rows = self._rows_saved is not None
+        if rows:
+            ops.gather_rows(dx_top, self._rows_saved[0].row_ids, out=self._rows_saved[0].dx)
         dx = dx_top
         pending = []
         dropping = any(d[1][1] for d in d_layers)
@@ -604,50 +807,57 @@ class Tagger:
             r = l % WGRAD_GROUP
             dh, dh1, dpre, dqkv = ac.dh[r], ac.dh1[r], ac.dpre[r], ac.dqkv[r]
             d_att, d_o, d_f = d_layers[l]
-            # with hidden dropout the sub-layer GEMMs see dY = mask * dh (dhm / dh1m); the residual branch keeps dh / dh1
-            dhm = dhm_ring[r] if d_f[1] else dh
-            dh1m = dh1m_ring[r] if d_o[1] else dh1
-            # LN2 backward; fused: d ffn2.bias = column sums of dh
-            ops.ln_bwd(dx, ac.h2[l], ac.st2[l][0], ac.st2[l][1], a.param(p + "ln2.g"), dh, a.grad(p + "ln2.g"),
-                       a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), dhm=dhm if d_f[1] else None, drop=d_f,
-                       defer_ws=defer_ln[2 * l + 1] if defer else None, dy_slabs=dx_slabs)
-            dx_slabs = None
-            if defer:
-                ln_items.append((defer_ln[2 * l + 1], a.grad(p + "ln2.g"), a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), ln_blocks))
-            # FFN down dgrad: dpre = (dh W2) * gelu'(pre)   (the derivative itself was saved by the forward epilogue)
-            # (its column sums = d ffn1.bias are accumulated by the same epilogue when the 256^2 kernel runs)
-            fused = ops.uses_256(Mp, F_, occupancy=True)
-            if fused:
-                # column sums (= d ffn1.bias) leave the epilogue as plain stores into a [2 * Mp/256, F] workspace, folded by a
-                # small reduce kernel: per-tile atomics onto the same 4096 addresses were what made this the slowest GEMM
-                if ac.colsum_ws is None:
-                    ac.colsum_ws = torch.empty((2 * (Mp // 128), F_), dtype=F32, device=self.device)
-                # ops.gemm reports the tile height of the kernel that ran (256 under dynamic tile draw, the static kernel's pick --
-                # also when the scheduler ring is used up -- otherwise): it decides how many workspace lines hold partial sums
-                cws = ac.colsum_ws_all[l] if defer else ac.colsum_ws
-                trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l],
-                                 epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=cws, occupancy=True)
-                if defer and 2 * (Mp // trows) <= 64:
-                    cs_items.append((cws, a.grad(p + "ffn1.bias"), 2 * (Mp // trows)))
-                else:
-                    ops.colsum_rows_f32(cws, 2 * (Mp // trows), a.grad(p + "ffn1.bias"))
+            if rows and l == L - 1:
+                # the last layer ran on the head's rows only: its sub-layers' backward on the compact rows -> the full dqkv, dh1
+                # at the head's rows of a zero buffer, and three weight-gradient problems whose reduction runs over Mc rows
+                dh1, wg = self._last_layer_rows_backward(ac, l, maskbias, d_layers[l], dqkv)
             else:
-                ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l], epi=EPI_DGELU, occupancy=True)
-                ops.colsum(dpre, a.grad(p + "ffn1.bias"))
-            dx1_slabs = self._long_k_gemm(GEMM_NN, dpre, a.bf(p + "ffn1.weight"), Mp, H, F_, ac.dx1, ac, addend=dh, finish=False)
-            if dx1_slabs is not None:
-                dx1_slabs = (dx1_slabs[0], dx1_slabs[1], dh)
-            # LN1 backward; fused: d o.bias
-            ops.ln_bwd(ac.dx1, ac.h1[l], ac.st1[l][0], ac.st1[l][1], a.param(p + "ln1.g"), dh1, a.grad(p + "ln1.g"),
-                       a.grad(p + "ln1.b"), a.grad(p + "o.bias"), dhm=dh1m if d_o[1] else None, drop=d_o,
-                       defer_ws=defer_ln[2 * l] if defer else None, dy_slabs=dx1_slabs)
-            if defer:
-                ln_items.append((defer_ln[2 * l], a.grad(p + "ln1.g"), a.grad(p + "ln1.b"), a.grad(p + "o.bias"), ln_blocks))
-            # attention output projection
-            ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), Mp, H, H, C=ac.dctx, occupancy=True)
-            # attention core (+ d qkv.bias = column sums of dqkv, accumulated inside the kernels)
-            ops.attn_bwd(ac.qkv[l], ac.ctx[l], ac.dctx, maskbias, ac.lse[l], ac.dws, dqkv, B, S, H, A, drop=d_att,
-                         dbias=a.grad(p + "qkv.bias"), ctx_lo=ac.ctx_lo[l] if self.ATTN_RESIDUAL else None)
+                # with hidden dropout the sub-layer GEMMs see dY = mask * dh (dhm / dh1m); the residual branch keeps dh / dh1
+                dhm = dhm_ring[r] if d_f[1] else dh
+                dh1m = dh1m_ring[r] if d_o[1] else dh1
+                # LN2 backward; fused: d ffn2.bias = column sums of dh
+                ops.ln_bwd(dx, ac.h2[l], ac.st2[l][0], ac.st2[l][1], a.param(p + "ln2.g"), dh, a.grad(p + "ln2.g"),
+                           a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), dhm=dhm if d_f[1] else None, drop=d_f,
+                           defer_ws=defer_ln[2 * l + 1] if defer else None, dy_slabs=dx_slabs)
+                dx_slabs = None
+                if defer:
+                    ln_items.append((defer_ln[2 * l + 1], a.grad(p + "ln2.g"), a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), ln_blocks))
+                # FFN down dgrad: dpre = (dh W2) * gelu'(pre)   (the derivative itself was saved by the forward epilogue)
+                # (its column sums = d ffn1.bias are accumulated by the same epilogue when the 256^2 kernel runs)
+                fused = ops.uses_256(Mp, F_, occupancy=True)
+                if fused:
+                    # column sums (= d ffn1.bias) leave the epilogue as plain stores into a [2 * Mp/256, F] workspace, folded by a
+                    # small reduce kernel: per-tile atomics onto the same 4096 addresses were what made this the slowest GEMM
+                    if ac.colsum_ws is None:
+                        ac.colsum_ws = torch.empty((2 * (Mp // 128), F_), dtype=F32, device=self.device)
+                    # ops.gemm reports the tile height of the kernel that ran (256 under dynamic tile draw, the static kernel's pick --
+                    # also when the scheduler ring is used up -- otherwise): it decides how many workspace lines hold partial sums
+                    cws = ac.colsum_ws_all[l] if defer else ac.colsum_ws
+                    trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l],
+                                     epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=cws, occupancy=True)
+                    if defer and 2 * (Mp // trows) <= 64:
+                        cs_items.append((cws, a.grad(p + "ffn1.bias"), 2 * (Mp // trows)))
+                    else:
+                        ops.colsum_rows_f32(cws, 2 * (Mp // trows), a.grad(p + "ffn1.bias"))
+                else:
+                    ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l], epi=EPI_DGELU, occupancy=True)
+                    ops.colsum(dpre, a.grad(p + "ffn1.bias"))
+                dx1_slabs = self._long_k_gemm(GEMM_NN, dpre, a.bf(p + "ffn1.weight"), Mp, H, F_, ac.dx1, ac, addend=dh, finish=False)
+                if dx1_slabs is not None:
+                    dx1_slabs = (dx1_slabs[0], dx1_slabs[1], dh)
+                # LN1 backward; fused: d o.bias
+                ops.ln_bwd(ac.dx1, ac.h1[l], ac.st1[l][0], ac.st1[l][1], a.param(p + "ln1.g"), dh1, a.grad(p + "ln1.g"),
+                           a.grad(p + "ln1.b"), a.grad(p + "o.bias"), dhm=dh1m if d_o[1] else None, drop=d_o,
+                           defer_ws=defer_ln[2 * l] if defer else None, dy_slabs=dx1_slabs)
+                if defer:
+                    ln_items.append((defer_ln[2 * l], a.grad(p + "ln1.g"), a.grad(p + "ln1.b"), a.grad(p + "o.bias"), ln_blocks))
+                # attention output projection
+                ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), Mp, H, H, C=ac.dctx, occupancy=True)
+                # attention core (+ d qkv.bias = column sums of dqkv, accumulated inside the kernels)
+                ops.attn_bwd(ac.qkv[l], ac.ctx[l], ac.dctx, maskbias, ac.lse[l], ac.dws, dqkv, B, S, H, A, drop=d_att,
+                             dbias=a.grad(p + "qkv.bias"), ctx_lo=ac.ctx_lo[l] if self.ATTN_RESIDUAL else None)
+                wg = [(dhm, ac.act[l], H, F_, p + "ffn2.weight", Mp), (dpre, ac.x1[l], F_, H, p + "ffn1.weight", Mp),
+                      (dh1m, ac.ctx[l], H, H, p + "o.weight", Mp)]
             # QKV projection
             # (the next layer's LN2 backward folds this GEMM's slabs itself -- the first launch of that layer, before anything
             #  else writes the slab buffer; layer 0's gradient goes to the embedding LayerNorm as bf16)
@@ -661,10 +871,9 @@ class Tagger:
                     ops.scatter_add_rows_ld(dout, col0, idx, ac.dx, n_, scale, de_, dl_)
             # weight gradients dW += dY^T X are deferred and launched for WGRAD_GROUP layers at once
             # (no split-K, no atomics; the dY buffers rotate so they stay live until the group is flushed)
-            pending += [(dhm, ac.act[l], H, F_, p + "ffn2.weight"), (dpre, ac.x1[l], F_, H, p + "ffn1.weight"),
-                        (dh1m, ac.ctx[l], H, H, p + "o.weight"), (dqkv, ac.x[l], 3 * H, H, p + "qkv.weight")]
+            pending += wg + [(dqkv, ac.x[l], 3 * H, H, p + "qkv.weight", Mp)]
             if l % WGRAD_GROUP == 0:
-                self._wgrads(pending, Mp)
+                self._wgrads(pending)
                 pending = []
                 if grad_ready is not None:
                     hi_l = min(l + WGRAD_GROUP, L)
@@ -674,6 +883,8 @@ class Tagger:
                     ops.sched_active(True)   # a collective is in flight from here to the end of this backward pass
             dx = ac.dx
         a.wgrad_stale = False   # every GEMM-weight gradient has been written by this pass
+        if rows:   # (every reader of the scattered dh1 is enqueued: its rows back to zero for the next pass)
+            self._clear_dh1_rows(ac)
         # small batches: the column-sum reductions of the pass (2 L LayerNorm partials -> gamma / beta / bias gradients, L FFN-up bias
         # workspaces) in two launches instead of 3 L
         # (the embedding LayerNorm's kernel also sets the optimizer's row flags of the rows it writes, and its partial sums join the batch)
@@ -687,17 +898,19 @@ class Tagger:
         for k in range(0, len(cs_items), 64):
             ops.colsum_rows_f32_batched(cs_items[k:k + 64], F_)
 
-    def _wgrads(self, pairs, Mp):
+    def _wgrads(self, pairs):
+        """pairs: (dY, X, N, K, weight name, rows): dW[N, K] += dY[:rows]^T X[:rows] -- `rows` is the token count of the layer's
+        buffers (the last layer's compact rows when it ran on the head's rows only)"""
         a = self.arena
-        if all(n_ % 256 == 0 and k_ % 256 == 0 for _, _, n_, k_, _ in pairs):
+        if all(n_ % 256 == 0 and k_ % 256 == 0 for _, _, n_, k_, _, _ in pairs):
             # the first backward pass after an optimizer step overwrites the stale gradients (Arena.wgrad_stale), later ones add
             epi = EPI_STORE32 if (a.wgrad_stale and a.wgrad_overwrite_ok) else EPI_RMW32
-            ops.gemm_grouped(GEMM_TN, [ops.make_problem(dy, x, n_, k_, Mp, C32=a.grad(nm), epi=epi)
-                                       for dy, x, n_, k_, nm in pairs])
+            ops.gemm_grouped(GEMM_TN, [ops.make_problem(dy, x, n_, k_, rows, C32=a.grad(nm), epi=epi)
+                                       for dy, x, n_, k_, nm, rows in pairs])
         else:
-            for dy, x, n_, k_, nm in pairs:
-                ops.gemm(GEMM_TN, dy, x, n_, k_, Mp, C32=a.grad(nm), epi=EPI_ATOMIC32,
-                         splitk=_splitk((n_ // 128) * (k_ // 128), Mp))
+            for dy, x, n_, k_, nm, rows in pairs:
+                ops.gemm(GEMM_TN, dy, x, n_, k_, rows, C32=a.grad(nm), epi=EPI_ATOMIC32,
+                         splitk=_splitk((n_ // 128) * (k_ // 128), rows))
 
     # ---------------------------------------------------------------- tagger head
     def _head_drop(self):
@@ -759,8 +972,17 @@ class Tagger:
         (em f32[B,nc,T], pooled bf16[B*nc,H], crow_idx, B, nc, R, S, drop); drop = this forward's _head_drop(), for its backward"""
         B, S = batch["B"], batch["S"]
         R = batch.get("R", B)  # encoder rows (> B when long sentences were split into sliding windows)
-        hidden = self.encoder_forward(batch["ids"], batch["pos_ids"], batch["maskbias"], R, S)
         nc = batch["ctags"].shape[1]
+        # HEAD_ROWS_ONLY: the last layer on the rows the head reads.  Needs the kept rows BEFORE the encoder runs, so the forward's
+        # dropout seeds are drawn here -- first, as the encoder draws them -- and WordDropout's positions second: the same stream of
+        # draws, hence the same masks, as the full path.
+        rows = (self.HEAD_ROWS_ONLY and self._last_layer_only and R == B and 4 * nc <= S and self.cfg.num_hidden_layers >= 1
+                and self.device.type == "cuda")
+        self.last_path = "head_rows" if rows else "full"
+        if rows:
+            seeds = self._site_seeds()
+        else:
+            hidden = self.encoder_forward(batch["ids"], batch["pos_ids"], batch["maskbias"], R, S)
         crow_idx = batch["crow_idx"]
         if self.training and self.word_dropout > 0.0 and "cpos" in batch:
             # WordDropout (flair/nn.py:176-183) on the [n,B,D] sentence tensor: token position k is zeroed for EVERY sentence
@@ -770,6 +992,9 @@ class Tagger:
             dropped = torch.from_numpy(self._last_word_dropped).to(self.device)
             cpos = batch["cpos"].long()
             crow_idx = torch.where(dropped[cpos.clamp(min=0)] & (cpos >= 0), torch.full_like(crow_idx, -1), crow_idx)
+        if rows:
+            hidden = self._encoder_forward(batch["ids"], batch["pos_ids"], batch["maskbias"], R, S, True, seeds=seeds,
+                                           head_rows=(crow_idx, nc))
         drop = self._head_drop()
         em, pooled = self.emissions(hidden, crow_idx, B, nc, drop, ac=self.acts(R, S))
         return em, pooled, crow_idx, B, nc, R, S, drop

@@ -77,6 +77,10 @@ SIGNATURES = {
     "kbner_splitk_finish": (c_int, [P, c_int, P, P, c_int, P, c_int, c_int, c_int, U32, U32, P]),
     "kbner_attn_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, U32, U32, P]),
     "kbner_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, U32, U32, P, P]),
+    "kbner_attn_rows_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, U32, U32, P]),
+    "kbner_attn_rows_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, U32, U32, P, P]),
+    "kbner_ln_bwd_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, U32, U32, P]),
+    "kbner_rows_drop_add": (c_int, [P, c_int, P, P, P, P, c_int, c_int, U32, U32, P]),
     "kbner_lstm_step": (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, P, c_int, c_int, c_int, P]),
     "kbner_lstm_seq": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "kbner_sqnorm_ws_floats": (c_int, []),

@@ -448,11 +448,19 @@ def ln_fwd_slabs(ws, splits, bias, addend, drop, h, gamma, beta, eps, y, mean, r
            ptr(h), ptr(gamma), ptr(beta), eps, ptr(y), ptr(mean), ptr(rstd), M, H, stream_ptr())
 
 
-def ln_bwd(dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias=None, dhm=None, drop=NO_DROP, defer_ws=None, dy_slabs=None):
+def ln_bwd(dy, h, mean, rstd, gamma, dh, dgamma, dbeta, dbias=None, dhm=None, drop=NO_DROP, defer_ws=None, dy_slabs=None, row_ids=None):
     """drop=(seed, thresh) with thresh != 0: also writes dhm = mask * dh / (1-p) (the dY of the GEMM behind the dropout).
     defer_ws (f32, >= ln_bwd_blocks(M) * 3 H): the per-block partial column sums stay there instead of being reduced into dgamma /
-    dbeta / dbias by a launch of their own -- the caller reduces a whole backward pass's worth with ln_colreduce_batched."""
+    dbeta / dbias by a launch of their own -- the caller reduces a whole backward pass's worth with ln_colreduce_batched.
+    row_ids (i32 [M]; compact rows, immediate reduction only): row r draws the mask bits of row row_ids[r]."""
     M, H = h.shape
+    if row_ids is not None:
+        _chk(row_ids, I32, "row_ids")
+        if dy_slabs is not None or defer_ws is not None or row_ids.numel() < M:
+            raise L.KbnerError("ln_bwd: row_ids [M] goes with a bf16 dy and the immediate column-sum reduction")
+        L.call("kbner_ln_bwd_rows", ptr(dy), ptr(h), ptr(mean), ptr(rstd), ptr(gamma), ptr(dh), ptr(dgamma), ptr(dbeta), ptr(dbias),
+               ptr(ln_ws(H, h.device)), M, H, ptr(dhm), ptr(row_ids), drop[0], drop[1], stream_ptr())
+        return
     if dy_slabs is not None:   # (ws f32[splits, M, H], splits, addend): dy = bf16(sum_s ws[s] + addend), folded on the way in
         sws, splits, sadd = dy_slabs
         _chk(sws, F32, "dy_slabs")
@@ -666,6 +674,44 @@ def attn_bwd(qkv, ctx, dctx, maskbias, lse, dws, dqkv, B, S, H, A, drop=NO_DROP,
     """dbias f32[3H] (optional): accumulates the column sums of dqkv (= d qkv.bias) inside the kernels"""
     L.call("kbner_attn_bwd", ptr(qkv), ptr(ctx), ptr(ctx_lo), ptr(dctx), ptr(maskbias), ptr(lse), ptr(dws), ptr(dqkv), B, S, H, A,
            drop[0], drop[1], ptr(dbias), stream_ptr())
+
+
+def attn_rows_fwd(qkv, maskbias, q_pos, ctx_c, o32, lse_c, B, S, H, A, drop=NO_DROP):
+    """attention of the queries q_pos i32[B, nq] (positions inside the sentence, < 0: none) against all keys of their sentence:
+    ctx_c bf16 / o32 f32 [>= B*nq, H] in list order (zero rows for "none"), lse_c f32 [B, A, nq] (include/kbner.h)"""
+    _chk(qkv, BF16, "qkv"); _chk(q_pos, I32, "q_pos"); _chk(ctx_c, BF16, "ctx_c"); _chk(o32, F32, "o32"); _chk(lse_c, F32, "lse_c")
+    nq = q_pos.numel() // B
+    if q_pos.numel() != B * nq or nq < 1 or ctx_c.numel() < B * nq * H or o32.numel() < B * nq * H or lse_c.numel() < B * A * nq:
+        raise L.KbnerError("attn_rows_fwd: q_pos [B, nq], ctx_c / o32 [>= B*nq, H], lse_c [B, A, nq]")
+    L.call("kbner_attn_rows_fwd", ptr(qkv), ptr(maskbias), ptr(q_pos), ptr(ctx_c), ptr(o32), ptr(lse_c), B, S, H, A, nq, drop[0], drop[1],
+           stream_ptr())
+
+
+def attn_rows_bwd(qkv, q_pos, dctx_c, o32, lse_c, maskbias, dqkv, B, S, H, A, drop=NO_DROP, dbias=None):
+    """its backward: dctx_c bf16 [>= B*nq, H] -> every row [0, B*S) of dqkv bf16 [>= B*S, 3H] (dK | dV of all keys, dQ at the listed
+    rows, zeros in the Q third of the others); dbias f32[3H] (optional) += column sums of dqkv"""
+    _chk(qkv, BF16, "qkv"); _chk(q_pos, I32, "q_pos"); _chk(dctx_c, BF16, "dctx_c"); _chk(o32, F32, "o32"); _chk(lse_c, F32, "lse_c")
+    _chk(dqkv, BF16, "dqkv")
+    nq = q_pos.numel() // B
+    if q_pos.numel() != B * nq or nq < 1 or dctx_c.numel() < B * nq * H or o32.numel() < B * nq * H or dqkv.numel() < B * S * 3 * H:
+        raise L.KbnerError("attn_rows_bwd: q_pos [B, nq], dctx_c / o32 [>= B*nq, H], dqkv [>= B*S, 3H]")
+    L.call("kbner_attn_rows_bwd", ptr(qkv), ptr(q_pos), ptr(dctx_c), ptr(o32), ptr(lse_c), ptr(maskbias), ptr(dqkv), B, S, H, A, nq,
+           drop[0], drop[1], ptr(dbias), stream_ptr())
+
+
+def rows_drop_add(y, row_ids, out, drop, bias=None, addend=None):
+    """out[r] = bf16(dropout(y[r] + bias) + addend[r]) with the mask bits of row row_ids[r] (< 0: none) of the site `drop`: hidden
+    dropout on compact rows.  y f32 or bf16 [R, H] (R = row_ids.numel() leading rows), out / addend bf16 [>= R, H]"""
+    _chk(row_ids, I32, "row_ids"); _chk(out, BF16, "out")
+    if y.dtype not in (F32, BF16) or not y.is_cuda or not y.is_contiguous():
+        raise L.KbnerError("rows_drop_add: y must be a contiguous cuda f32 or bf16 tensor")
+    R, H = row_ids.numel(), y.shape[-1]
+    if y.shape[0] < R or out.shape[0] < R or out.shape[-1] != H or (addend is not None and (addend.shape[0] < R or addend.shape[-1] != H)):
+        raise L.KbnerError("rows_drop_add: y, out, addend [>= R, H]")
+    if addend is not None:
+        _chk(addend, BF16, "addend")
+    L.call("kbner_rows_drop_add", ptr(y), 1 if y.dtype == F32 else 0, ptr(bias), ptr(addend), ptr(row_ids), ptr(out), R, H,
+           int(drop[0]) & 0xFFFFFFFF, int(drop[1]), stream_ptr())
 
 
 # ---------------------------------------------------------------- LSTM (inference)
