@@ -12,6 +12,7 @@ Data layout in HBM (sized for 288 GB: everything stays resident, nothing is reco
 """
 import logging
 import math
+import weakref
 
 import torch
 
@@ -220,30 +221,44 @@ def hf_name_map(cfg):
     return m
 
 
+class _LayerView:
+    """one layer's buffers of an _Acts under the names a _RowView gives the compact set: either is a buffer set of
+    Tagger._sublayers_forward / _sublayers_backward.  Built once per activation set, never per step."""
+    row_ids = split_as = None     # (every row stands for itself)
+
+    def __init__(self, ac, l, ctx, h1, x1, dact, act, h2, st1, st2):
+        r = l % WGRAD_GROUP
+        # ws: the owner of splitk_ws / colsum_ws, one of each for all layers.  Not a reference cycle: a set that Tagger.acts evicts
+        # must give its memory back at once, not at the next garbage collection
+        self.M, self.ws = ac.Mp, weakref.proxy(ac)
+        self.xres, self.xo = ac.x[l], ac.x[l + 1]
+        self.ctx, self.h1, self.x1, self.dact, self.act, self.h2 = ctx, h1, x1, dact, act, h2
+        (self.st1a, self.st1b), (self.st2a, self.st2b) = st1, st2
+        self.dh, self.dh1, self.dpre, self.dx1, self.dctx = ac.dh[r], ac.dh1[r], ac.dpre[r], ac.dx1, ac.dctx
+        self.dhm = self.dh1m = None     # (_Acts.drop_buffers)
+
+
 class _Acts:
     """Activation / workspace buffers for one (B, S) shape; zero-initialised so the 128-row padding
     tail never feeds NaNs into a wgrad reduction."""
 
-    def __init__(self, cfg, B, S, device):
+    def __init__(self, cfg, B, S, device, nbytes):
         H, F_, A, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
         self.B, self.S, self.M = B, S, B * S
         self.Mp = Mp = _round_up(B * S, 256)
+        self.nbytes = nbytes       # what Tagger.acts budgets for the set (+ the compact set's, once head_rows has made it)
         z = lambda *shape, dt=BF16: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
         self.h0 = z(Mp, H)
         self.emb_mean, self.emb_rstd = z(Mp, dt=F32), z(Mp, dt=F32)
         self.x = [z(Mp, H) for _ in range(L + 1)]
         self.qkv = [z(Mp, 3 * H) for _ in range(L)]
-        self.ctx = [z(Mp, H) for _ in range(L)]
+        ctx = [z(Mp, H) for _ in range(L)]
         self.ctx_lo = [None] * L   # O - bf16(O) in bytes, allocated by the first training forward (Engine.ATTN_RESIDUAL)
         self.infer_graph = None    # Engine.encoder_forward(need_grad=False): static inputs + the captured HIP graph of this shape
         self.lse = [z(B, A, S, dt=F32) for _ in range(L)]
-        self.h1 = [z(Mp, H) for _ in range(L)]
-        self.x1 = [z(Mp, H) for _ in range(L)]
-        self.dact = [z(Mp, F_) for _ in range(L)]  # gelu'(pre-activation), saved by the FFN-up epilogue for backward
-        self.act = [z(Mp, F_) for _ in range(L)]
-        self.h2 = [z(Mp, H) for _ in range(L)]
-        self.st1 = [(z(Mp, dt=F32), z(Mp, dt=F32)) for _ in range(L)]
-        self.st2 = [(z(Mp, dt=F32), z(Mp, dt=F32)) for _ in range(L)]
+        # per layer, handed to its view below: h1, x1, gelu'(pre-activation) saved by the FFN-up epilogue for backward, act, h2, LN stats
+        per_layer = [ctx] + [[z(Mp, W) for _ in range(L)] for W in (H, H, F_, F_, H)]
+        per_layer += [[(z(Mp, dt=F32), z(Mp, dt=F32)) for _ in range(L)] for _ in range(2)]
         # backward workspaces (shared across layers)
         # dY buffers are kept for WGRAD_GROUP layers so their weight-gradient GEMMs can be launched
         # together (4 layers x 4 GEMMs = 768 tiles of 256x256 = 3 full waves of the 256 CUs)
@@ -257,6 +272,7 @@ class _Acts:
         self.dws = z(B, A, S, dt=F32)
         self._z, self._H = z, H
         self.dhm = self.dh1m = None
+        self.layers = [_LayerView(self, l, *(field[l] for field in per_layer)) for l in range(L)]
         self.splitk_ws = None  # f32 [4, Mp, H] split-K slabs, allocated on first use (small micro-batches only)
         self.colsum_ws = None  # f32 [2 * Mp/256, F] column-sum lines of the FFN-down dgrad epilogue (EPI_COLSUM_WS)
         self.defer_ln_ws = None     # small batches: one partial-sum workspace per LayerNorm / per FFN-up bias (Tagger.encoder_backward)
@@ -271,21 +287,21 @@ class _Acts:
         """the compact activation set, viewed at nc kept tokens per sentence.  ONE set per (B, S) shape, sized for the most rows the
         path takes (4 * nc <= S): a batch with another nc re-uses it through a view, nothing is re-allocated or re-filled."""
         if self.rows is None:
-            self.rows = _RowActs(cfg, self.B, self.S, _round_up(self.B * (self.S // 4), 256), self._z, self.h0.device)
+            self.rows = _RowActs(cfg, self.Mp, _round_up(self.B * (self.S // 4), 256), self._z, self.h0.device)
             self.dh1_full = self._z(self.Mp, self._H)
         if dropping:
             self.rows.drop_buffers()
         counted = self.rows.nbytes + 2 * self.Mp * self._H
-        self.nbytes = getattr(self, "nbytes", 0) + counted - self._rows_counted
+        self.nbytes += counted - self._rows_counted
         self._rows_counted = counted
         return self.rows.at(_round_up(self.B * nc, 256))
 
     def drop_buffers(self):
         """masked copies of dh / dh1 (the dY of the two GEMMs whose outputs were dropped); allocated on first training use"""
         if self.dhm is None:
-            self.dhm = [self._z(self.Mp, self._H) for _ in range(WGRAD_GROUP)]
-            self.dh1m = [self._z(self.Mp, self._H) for _ in range(WGRAD_GROUP)]
-        return self.dhm, self.dh1m
+            self.dhm, self.dh1m = ([self._z(self.Mp, self._H) for _ in range(WGRAD_GROUP)] for _ in range(2))
+            for l, v in enumerate(self.layers):
+                v.dhm, v.dh1m = self.dhm[l % WGRAD_GROUP], self.dh1m[l % WGRAD_GROUP]
 
 
 class _RowActs:
@@ -295,9 +311,9 @@ class _RowActs:
     and -1 rows enter weight-gradient products and column sums (their dY rows are exact zeros, so whatever finite value the forward
     leaves in them contributes nothing)."""
 
-    def __init__(self, cfg, B, S, cap, z, device):
+    def __init__(self, cfg, split_as, cap, z, device):
         H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        self.cap = cap
+        self.cap, self.split_as = cap, split_as     # (split_as: the rows of the activation set whose last layer this is)
         self.row_ids = torch.full((cap,), -1, dtype=I32, device=device)
         self.ctx, self.o32, self.lse = z(cap, H), z(cap, H, dt=F32), z(A * cap, dt=F32)
         self.xres, self.h1, self.x1, self.h2, self.xo = (z(cap, H) for _ in range(5))
@@ -325,18 +341,20 @@ class _RowActs:
 
 
 class _RowView:
-    """the leading Mc rows of a _RowActs (every buffer sliced on first use), plus what belongs to that row count alone"""
+    """the leading M = Mc rows of a _RowActs (every buffer sliced on first use), plus what belongs to that row count alone.  The
+    same names as a _LayerView's: either is a buffer set of Tagger._sublayers_forward / _sublayers_backward."""
 
     def __init__(self, acts, Mc):
         assert Mc <= acts.cap
-        self._acts, self.Mc, self.n_used, self.sent_base = acts, Mc, -1, None
-        self.splitk_ws = self.colsum_ws = None     # (_long_k_gemm's slabs, the FFN-down dgrad's column-sum lines: sized by Mc)
+        self._acts, self.M, self.split_as, self.n_used, self.sent_base = acts, Mc, acts.split_as, -1, None
+        self.ws = self     # (_long_k_gemm's slabs, the FFN-down dgrad's column-sum lines: sized by Mc, so the view's own)
+        self.splitk_ws = self.colsum_ws = None
 
     def __getattr__(self, name):     # (only reached for names not set yet)
         t = getattr(self._acts, name)
         if t is None:
             return None
-        v = t if name == "lse" else t[:self.Mc]
+        v = t if name == "lse" else t[:self.M]
         setattr(self, name, v)
         return v
 
@@ -521,9 +539,7 @@ class Tagger:
         need = int(_round_up(B * S, 256) * per_row)
         while self._acts and sum(a.nbytes for a in self._acts.values()) + need > self.ACTS_BUDGET_BYTES:
             self._acts.pop(next(iter(self._acts)))
-        ac = _Acts(self.cfg, B, S, self.device)
-        ac.nbytes = need
-        self._acts[key] = ac
+        ac = self._acts[key] = _Acts(self.cfg, B, S, self.device, need)
         return ac
 
     SPLITK_MAX_TILES = 64  # outputs with at most this many 256x256 tiles split a long K (small micro-batches)
@@ -621,10 +637,9 @@ class Tagger:
         seeds: this forward's _site_seeds() when the caller has drawn them already.  head_rows = (row_idx i32[B*nc], nc): the last
         layer runs on these rows only (_last_layer_rows_forward) -- of the returned hidden state only they are written."""
         cfg, a = self.cfg, self.arena
-        H, F_, A, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
+        H, A, L, eps = cfg.hidden_size, cfg.num_attention_heads, cfg.num_hidden_layers, cfg.layer_norm_eps
         ac = self.acts(B, S)
         Mp = ac.Mp
-        eps = cfg.layer_norm_eps
         d_emb, d_layers = self._site_seeds() if seeds is None else seeds
         self._rows_saved = None
         a.catch_up_rows(ids)   # FusedAdamW.lazy_rows: the looked-up rows owe the zero-gradient steps since they were last touched
@@ -632,50 +647,125 @@ class Tagger:
                          a.param("emb.ln.b"), eps, ac.h0, ac.x[0], ac.emb_mean, ac.emb_rstd, drop=d_emb)
         for l in range(L):
             p = "l%d." % l
-            x = ac.x[l]
-            d_att, d_o, d_f = d_layers[l]
-            ops.gemm(GEMM_NT, x, a.bf(p + "qkv.weight"), Mp, 3 * H, H, C=ac.qkv[l], bias=a.param(p + "qkv.bias"), epi=EPI_BIAS, occupancy=True)
+            ops.gemm(GEMM_NT, ac.x[l], a.bf(p + "qkv.weight"), Mp, 3 * H, H, C=ac.qkv[l], bias=a.param(p + "qkv.bias"), epi=EPI_BIAS,
+                     occupancy=True)
             if head_rows is not None and l == L - 1:
                 self._last_layer_rows_forward(ac, l, maskbias, d_layers[l], head_rows[0], head_rows[1])
                 break
             if need_grad and self.ATTN_RESIDUAL and ac.ctx_lo[l] is None:
                 ac.ctx_lo[l] = torch.empty((Mp * H,), dtype=torch.uint8, device=self.device)   # what the backward reads is written
-            ops.attn_fwd(ac.qkv[l], maskbias, ac.ctx[l], ac.lse[l], B, S, H, A, drop=d_att,
+            ops.attn_fwd(ac.qkv[l], maskbias, ac.layers[l].ctx, ac.lse[l], B, S, H, A, drop=d_layers[l][0],
                          ctx_lo=ac.ctx_lo[l] if need_grad and self.ATTN_RESIDUAL else None)
-            ops.gemm(GEMM_NT, ac.ctx[l], a.bf(p + "o.weight"), Mp, H, H, C=ac.h1[l], bias=a.param(p + "o.bias"), addend=x,
-                     epi=EPI_BIAS | EPI_ADD, drop=d_o, occupancy=True)
-            ops.ln_fwd(ac.h1[l], a.param(p + "ln1.g"), a.param(p + "ln1.b"), eps, ac.x1[l], ac.st1[l][0], ac.st1[l][1])
-            if need_grad:
-                ops.gemm(GEMM_NT, ac.x1[l], a.bf(p + "ffn1.weight"), Mp, F_, H, C=ac.act[l], out2=ac.dact[l],
-                         bias=a.param(p + "ffn1.bias"), epi=EPI_BIAS | EPI_GELU, occupancy=True)
-            else:
-                ops.gemm(GEMM_NT, ac.x1[l], a.bf(p + "ffn1.weight"), Mp, F_, H, C=ac.act[l],
-                         bias=a.param(p + "ffn1.bias"), epi=EPI_BIAS | EPI_GELU_FWD, occupancy=True)
-            slabs = self._long_k_gemm(GEMM_NT, ac.act[l], a.bf(p + "ffn2.weight"), Mp, H, F_, ac.h2[l], ac, bias=a.param(p + "ffn2.bias"),
-                                      addend=ac.x1[l], drop=d_f, finish=False)
-            if slabs is not None:   # small micro-batches: h2 = fold of the split-K slabs, written by the LayerNorm kernel itself
-                ops.ln_fwd_slabs(slabs[0], slabs[1], a.param(p + "ffn2.bias"), ac.x1[l], d_f, ac.h2[l], a.param(p + "ln2.g"),
-                                 a.param(p + "ln2.b"), eps, ac.x[l + 1], ac.st2[l][0], ac.st2[l][1])
-            else:
-                ops.ln_fwd(ac.h2[l], a.param(p + "ln2.g"), a.param(p + "ln2.b"), eps, ac.x[l + 1], ac.st2[l][0], ac.st2[l][1])
+            self._sublayers_forward(ac.layers[l], l, d_layers[l], need_grad)
         self._enc_saved = (ids, pos_ids, maskbias, B, S, d_emb, d_layers) if need_grad else None
         return ac.x[L]
+
+    # ---------------------------------------------------------------- one layer behind its attention, on a buffer set
+    @staticmethod
+    def _occ(v, N):
+        """occupancy= of an [v.M, N] GEMM: compact rows run on the kernel (256- or 128-row tiles) the same GEMM over the v.split_as
+        rows they are taken from runs on -- a row's sum is the same; a layer's own rows follow the occupancy rule itself"""
+        return v.split_as is None or not ops.uses_256(v.split_as, N, occupancy=True)
+
+    def _gemm_drop_add(self, v, A, name, K, out, addend, drop, long_k=False):
+        """out bf16 [v.M, H] = dropout(A . W^T + bias) + addend, the two sub-layer outputs (name "l3.o" / "l3.ffn2"), in the GEMM's
+        epilogue.  Compact rows (v.row_ids) draw the mask bits of the ORIGINAL rows: the GEMM leaves unrounded fp32 (plain stores on the
+        256-row kernel, zero + fp32 adds on the 128-row one), kbner_rows_drop_add applies bias, mask and residual with one rounding.
+        long_k: through _long_k_gemm -> its split-K slabs for the LayerNorm behind to fold (out is NOT written), or None."""
+        M, H, occ = v.M, self.cfg.hidden_size, self._occ(v, self.cfg.hidden_size)
+        W, bias = self.arena.bf(name + ".weight"), self.arena.param(name + ".bias")
+        if v.row_ids is not None and drop[1]:
+            big = ops.uses_256(M, H, occupancy=occ)
+            if not big:
+                v.y32.zero_()
+            ops.gemm(GEMM_NT, A, W, M, H, K, C32=v.y32, epi=EPI_STORE32 if big else EPI_ATOMIC32, occupancy=occ)
+            return ops.rows_drop_add(v.y32, v.row_ids, out, drop, bias=bias, addend=addend)
+        if v.row_ids is not None:
+            drop = ops.NO_DROP
+        if long_k:
+            return self._long_k_gemm(GEMM_NT, A, W, M, H, K, out, v.ws, bias=bias, addend=addend, drop=drop, finish=False, split_as=v.split_as)
+        ops.gemm(GEMM_NT, A, W, M, H, K, C=out, bias=bias, addend=addend, epi=EPI_BIAS | EPI_ADD, drop=drop, occupancy=occ)
+
+    def _sublayers_forward(self, v, l, drops, need_grad=True):
+        """Layer l from its attention output v.ctx and its input v.xres to v.xo: output projection, LN1, FFN, LN2 on the v.M rows of
+        the buffer set v -- a layer of the activation set (_Acts.layers) or the head's rows of the last one (_RowView)."""
+        cfg, a = self.cfg, self.arena
+        H, F_, eps, p = cfg.hidden_size, cfg.intermediate_size, cfg.layer_norm_eps, "l%d." % l
+        self._gemm_drop_add(v, v.ctx, p + "o", H, v.h1, v.xres, drops[1])
+        ops.ln_fwd(v.h1, a.param(p + "ln1.g"), a.param(p + "ln1.b"), eps, v.x1, v.st1a, v.st1b)
+        # (inference: without the gelu' output that only the backward reads)
+        ops.gemm(GEMM_NT, v.x1, a.bf(p + "ffn1.weight"), v.M, F_, H, C=v.act, out2=v.dact if need_grad else None,
+                 bias=a.param(p + "ffn1.bias"), epi=EPI_BIAS | (EPI_GELU if need_grad else EPI_GELU_FWD), occupancy=self._occ(v, F_))
+        slabs = self._gemm_drop_add(v, v.act, p + "ffn2", F_, v.h2, v.x1, drops[2], long_k=True)
+        if slabs is not None:   # small micro-batches: h2 = fold of the split-K slabs, written by the LayerNorm kernel itself
+            ops.ln_fwd_slabs(slabs[0], slabs[1], a.param(p + "ffn2.bias"), v.x1, drops[2] if v.row_ids is None else ops.NO_DROP, v.h2,
+                             a.param(p + "ln2.g"), a.param(p + "ln2.b"), eps, v.xo, v.st2a, v.st2b)
+        else:
+            ops.ln_fwd(v.h2, a.param(p + "ln2.g"), a.param(p + "ln2.b"), eps, v.xo, v.st2a, v.st2b)
+
+    def _sublayers_backward(self, v, l, dx, drops, dx_slabs=None, defer=None):
+        """backward of _sublayers_forward on the same buffer set, from dx = d loss / d v.xo (or the split-K slabs dx_slabs standing in
+        for it) to v.dctx and v.dh1, the residual gradient into the layer's input; bias, gamma and beta gradients into arena.g.
+        defer = encoder_backward's (LayerNorm workspaces, column-sum workspaces, ln_items, cs_items, ln_blocks): the column sums stay
+        in layer l's workspaces and join the items the pass reduces at its end.  -> the three weight-gradient problems for _wgrads."""
+        cfg, a = self.cfg, self.arena
+        H, F_, M, p = cfg.hidden_size, cfg.intermediate_size, v.M, "l%d." % l
+        _, d_o, d_f = drops
+        occ_f = self._occ(v, F_)
+        # with hidden dropout the sub-layer GEMMs see dY = mask * dh (dhm / dh1m; compact rows draw the mask bits of the ORIGINAL
+        # rows); the residual branch keeps dh / dh1
+        dh, dh1, dpre, dhm, dh1m = v.dh, v.dh1, v.dpre, v.dhm if d_f[1] else v.dh, v.dh1m if d_o[1] else v.dh1
+        ln2_ws = ln1_ws = None
+        if defer is not None:
+            defer_ln, colsum_all, ln_items, cs_items, ln_blocks = defer
+            ln2_ws, ln1_ws = defer_ln[2 * l + 1], defer_ln[2 * l]
+        # LN2 backward; fused: d ffn2.bias = column sums of dh
+        ops.ln_bwd(dx, v.h2, v.st2a, v.st2b, a.param(p + "ln2.g"), dh, a.grad(p + "ln2.g"), a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"),
+                   dhm=dhm if d_f[1] else None, drop=d_f, defer_ws=ln2_ws, dy_slabs=dx_slabs, row_ids=v.row_ids if d_f[1] else None)
+        if defer is not None:
+            ln_items.append((ln2_ws, a.grad(p + "ln2.g"), a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), ln_blocks))
+        # FFN down dgrad: dpre = (dh W2) * gelu'(pre)   (the derivative itself was saved by the forward epilogue)
+        # (its column sums = d ffn1.bias are accumulated by the same epilogue when the 256^2 kernel runs)
+        if ops.uses_256(M, F_, occupancy=occ_f):
+            # column sums (= d ffn1.bias) leave the epilogue as plain stores into a [2 * M/256, F] workspace, folded by a
+            # small reduce kernel: per-tile atomics onto the same 4096 addresses were what made this the slowest GEMM
+            if v.ws.colsum_ws is None:
+                v.ws.colsum_ws = torch.empty((2 * (M // 128), F_), dtype=F32, device=self.device)
+            # ops.gemm reports the tile height of the kernel that ran (256 under dynamic tile draw, the static kernel's pick --
+            # also when the scheduler ring is used up -- otherwise): it decides how many workspace lines hold partial sums
+            cws = colsum_all[l] if defer is not None else v.ws.colsum_ws
+            trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), M, F_, H, C=dpre, aux=v.dact,
+                             epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=cws, occupancy=occ_f)
+            if defer is not None and 2 * (M // trows) <= 64:
+                cs_items.append((cws, a.grad(p + "ffn1.bias"), 2 * (M // trows)))
+            else:
+                ops.colsum_rows_f32(cws, 2 * (M // trows), a.grad(p + "ffn1.bias"))
+        else:
+            ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), M, F_, H, C=dpre, aux=v.dact, epi=EPI_DGELU, occupancy=occ_f)
+            ops.colsum(dpre, a.grad(p + "ffn1.bias"))
+        # (the row-keyed LayerNorm backward reads a bf16 dy: with dropout on compact rows a split-K GEMM folds its slabs itself)
+        dx1_slabs = self._long_k_gemm(GEMM_NN, dpre, a.bf(p + "ffn1.weight"), M, H, F_, v.dx1, v.ws, addend=dh,
+                                      finish=v.row_ids is not None and bool(d_o[1]), split_as=v.split_as)
+        if dx1_slabs is not None:
+            dx1_slabs = (dx1_slabs[0], dx1_slabs[1], dh)
+        # LN1 backward; fused: d o.bias
+        ops.ln_bwd(v.dx1, v.h1, v.st1a, v.st1b, a.param(p + "ln1.g"), dh1, a.grad(p + "ln1.g"), a.grad(p + "ln1.b"), a.grad(p + "o.bias"),
+                   dhm=dh1m if d_o[1] else None, drop=d_o, defer_ws=ln1_ws, dy_slabs=dx1_slabs, row_ids=v.row_ids if d_o[1] else None)
+        if defer is not None:
+            ln_items.append((ln1_ws, a.grad(p + "ln1.g"), a.grad(p + "ln1.b"), a.grad(p + "o.bias"), ln_blocks))
+        # attention output projection
+        ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), M, H, H, C=v.dctx, occupancy=self._occ(v, H))
+        return [(dhm, v.act, H, F_, p + "ffn2.weight", M), (dpre, v.x1, F_, H, p + "ffn1.weight", M), (dh1m, v.ctx, H, H, p + "o.weight", M)]
 
     # ---------------------------------------------------------------- the last layer on the head's rows (HEAD_ROWS_ONLY)
     def _last_layer_rows_forward(self, ac, l, maskbias, drops, row_idx, nc):
         """Layer l behind its QKV projection, for the encoder rows row_idx i32[B*nc] (-1: none) only: few-query attention against
-        the full K / V, then output projection, LN1, FFN and LN2 on the compact rows.  The results are scattered into ac.x[l + 1] at
-        their rows, where the head's gather finds them; everything the backward needs stays in ac.rows.
-        Hidden dropout draws the bits of the ORIGINAL rows: the compact GEMM leaves fp32, kbner_rows_drop_add applies bias, mask and
-        residual with one rounding, as the fused epilogue of the full path does."""
-        cfg, a = self.cfg, self.arena
-        H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        B, S, eps, p = ac.B, ac.S, cfg.layer_norm_eps, "l%d." % l
-        d_att, d_o, d_f = drops
-        rw = ac.head_rows(cfg, nc, dropping=bool(d_o[1] or d_f[1]))
-        Mc, n = rw.Mc, B * nc
-        # every compact GEMM runs on the kernel (256- or 128-row tiles) its full counterpart runs on: a row's sum is the same
-        occ = lambda N: not ops.uses_256(ac.Mp, N, occupancy=True)  # noqa: E731
+        the full K / V, then _sublayers_forward on the compact rows.  The results are scattered into ac.x[l + 1] at their rows,
+        where the head's gather finds them; everything the backward needs stays in ac.rows."""
+        cfg = self.cfg
+        H, A, B, S = cfg.hidden_size, cfg.num_attention_heads, ac.B, ac.S
+        rw = ac.head_rows(cfg, nc, dropping=bool(drops[1][1] or drops[2][1]))
+        n = B * nc
         if rw.n_used != n:     # (per view: the sentence offsets of this row count)
             rw.sent_base = (torch.arange(n, dtype=I32, device=self.device) // nc) * S
             rw.n_used = n
@@ -685,29 +775,9 @@ class Tagger:
             ac.rows.last_n = n
         rw.row_ids[:n].copy_(row_idx)
         q_pos = torch.where(row_idx >= 0, row_idx - rw.sent_base, row_idx).contiguous()
-        ops.attn_rows_fwd(ac.qkv[l], maskbias, q_pos, rw.ctx, rw.o32, rw.lse, B, S, H, A, drop=d_att)
+        ops.attn_rows_fwd(ac.qkv[l], maskbias, q_pos, rw.ctx, rw.o32, rw.lse, B, S, H, A, drop=drops[0])
         ops.gather_rows(ac.x[l], rw.row_ids, out=rw.xres)
-        if d_o[1]:
-            self._gemm_nt_f32(rw.ctx, a.bf(p + "o.weight"), Mc, H, H, rw.y32, occ(H))
-            ops.rows_drop_add(rw.y32, rw.row_ids, rw.h1, d_o, bias=a.param(p + "o.bias"), addend=rw.xres)
-        else:
-            ops.gemm(GEMM_NT, rw.ctx, a.bf(p + "o.weight"), Mc, H, H, C=rw.h1, bias=a.param(p + "o.bias"), addend=rw.xres,
-                     epi=EPI_BIAS | EPI_ADD, occupancy=occ(H))
-        ops.ln_fwd(rw.h1, a.param(p + "ln1.g"), a.param(p + "ln1.b"), eps, rw.x1, rw.st1a, rw.st1b)
-        ops.gemm(GEMM_NT, rw.x1, a.bf(p + "ffn1.weight"), Mc, F_, H, C=rw.act, out2=rw.dact, bias=a.param(p + "ffn1.bias"),
-                 epi=EPI_BIAS | EPI_GELU, occupancy=occ(F_))
-        slabs = None
-        if d_f[1]:
-            self._gemm_nt_f32(rw.act, a.bf(p + "ffn2.weight"), Mc, H, F_, rw.y32, occ(H))
-            ops.rows_drop_add(rw.y32, rw.row_ids, rw.h2, d_f, bias=a.param(p + "ffn2.bias"), addend=rw.x1)
-        else:
-            slabs = self._long_k_gemm(GEMM_NT, rw.act, a.bf(p + "ffn2.weight"), Mc, H, F_, rw.h2, rw, bias=a.param(p + "ffn2.bias"),
-                                      addend=rw.x1, finish=False, split_as=ac.Mp)
-        if slabs is not None:
-            ops.ln_fwd_slabs(slabs[0], slabs[1], a.param(p + "ffn2.bias"), rw.x1, ops.NO_DROP, rw.h2, a.param(p + "ln2.g"),
-                             a.param(p + "ln2.b"), eps, rw.xo, rw.st2a, rw.st2b)
-        else:
-            ops.ln_fwd(rw.h2, a.param(p + "ln2.g"), a.param(p + "ln2.b"), eps, rw.xo, rw.st2a, rw.st2b)
+        self._sublayers_forward(rw, l, drops)
         ops.scatter_rows(rw.xo, rw.row_ids, ac.x[l + 1])
         self._rows_saved = (rw, q_pos, nc)
 
@@ -718,53 +788,19 @@ class Tagger:
             ops.scatter_rows(ac.rows.zeros[:ac.dh1_rows.numel()], ac.dh1_rows, ac.dh1_full)
             ac.dh1_rows = None
 
-    @staticmethod
-    def _gemm_nt_f32(A, W, M, N, K, y32, occupancy):
-        """y32 f32[M, N] = A . W^T, unrounded: plain fp32 stores on the 256-row kernel, zero + fp32 adds on the 128-row one"""
-        if ops.uses_256(M, N, occupancy=occupancy):
-            ops.gemm(GEMM_NT, A, W, M, N, K, C32=y32, epi=EPI_STORE32, occupancy=occupancy)
-        else:
-            y32.zero_()
-            ops.gemm(GEMM_NT, A, W, M, N, K, C32=y32, epi=EPI_ATOMIC32, occupancy=occupancy)
-
     def _last_layer_rows_backward(self, ac, l, maskbias, drops, dqkv):
-        """backward of _last_layer_rows_forward from rw.dx (d loss / d the compact output rows; -1 and pad rows zero): the bias,
-        gamma and beta gradients into arena.g, the full dqkv of the layer, and -> (dh1 scattered to its encoder rows in an otherwise
+        """backward of _last_layer_rows_forward from rw.dx (d loss / d the compact output rows; -1 and pad rows zero):
+        _sublayers_backward on the compact rows, the full dqkv of the layer, and -> (dh1 scattered to its encoder rows in an otherwise
         zero [Mp, H] buffer: the residual gradient into x[l], the three compact weight-gradient problems for _wgrads)."""
-        cfg, a = self.cfg, self.arena
-        H, F_, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        B, S, p = ac.B, ac.S, "l%d." % l
-        d_att, d_o, d_f = drops
+        cfg = self.cfg
         rw, q_pos, _ = self._rows_saved
-        Mc = rw.Mc
-        occ = lambda N: not ops.uses_256(ac.Mp, N, occupancy=True)  # noqa: E731  (as in the forward)
-        dhm = rw.dhm if d_f[1] else rw.dh
-        dh1m = rw.dh1m if d_o[1] else rw.dh1
         self._clear_dh1_rows(ac)   # (only after a backward pass that did not reach its end)
-        # LN2 backward (fused: d ffn2.bias); with hidden dropout dhm = mask * dh draws the mask bits of the ORIGINAL rows
-        ops.ln_bwd(rw.dx, rw.h2, rw.st2a, rw.st2b, a.param(p + "ln2.g"), rw.dh, a.grad(p + "ln2.g"), a.grad(p + "ln2.b"),
-                   a.grad(p + "ffn2.bias"), dhm=dhm if d_f[1] else None, drop=d_f, row_ids=rw.row_ids if d_f[1] else None)
-        if ops.uses_256(Mc, F_, occupancy=occ(F_)):
-            if rw.colsum_ws is None:
-                rw.colsum_ws = torch.empty((2 * (Mc // 128), F_), dtype=F32, device=self.device)
-            trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mc, F_, H, C=rw.dpre, aux=rw.dact,
-                             epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=rw.colsum_ws, occupancy=occ(F_))
-            ops.colsum_rows_f32(rw.colsum_ws, 2 * (Mc // trows), a.grad(p + "ffn1.bias"))
-        else:
-            ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mc, F_, H, C=rw.dpre, aux=rw.dact, epi=EPI_DGELU, occupancy=occ(F_))
-            ops.colsum(rw.dpre, a.grad(p + "ffn1.bias"))
-        # (the row-keyed LayerNorm backward reads a bf16 dy: with dropout a split-K GEMM folds its slabs itself)
-        slabs = self._long_k_gemm(GEMM_NN, rw.dpre, a.bf(p + "ffn1.weight"), Mc, H, F_, rw.dx1, rw, addend=rw.dh, finish=bool(d_o[1]), split_as=ac.Mp)
-        if slabs is not None:
-            slabs = (slabs[0], slabs[1], rw.dh)
-        ops.ln_bwd(rw.dx1, rw.h1, rw.st1a, rw.st1b, a.param(p + "ln1.g"), rw.dh1, a.grad(p + "ln1.g"), a.grad(p + "ln1.b"),
-                   a.grad(p + "o.bias"), dhm=dh1m if d_o[1] else None, drop=d_o, dy_slabs=slabs, row_ids=rw.row_ids if d_o[1] else None)
-        ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), Mc, H, H, C=rw.dctx, occupancy=occ(H))
-        ops.attn_rows_bwd(ac.qkv[l], q_pos, rw.dctx, rw.o32, rw.lse, maskbias, dqkv, B, S, H, A, drop=d_att, dbias=a.grad(p + "qkv.bias"))
+        wg = self._sublayers_backward(rw, l, rw.dx, drops)
+        ops.attn_rows_bwd(ac.qkv[l], q_pos, rw.dctx, rw.o32, rw.lse, maskbias, dqkv, ac.B, ac.S, cfg.hidden_size, cfg.num_attention_heads,
+                          drop=drops[0], dbias=self.arena.grad("l%d.qkv.bias" % l))
         ac.dh1_rows = rw.row_ids.clone()     # (zeroed again at the end of the pass -- or, had it not got there, below)
         ops.scatter_rows(rw.dh1, ac.dh1_rows, ac.dh1_full)
-        return ac.dh1_full, [(dhm, rw.act, H, F_, p + "ffn2.weight", Mc), (rw.dpre, rw.x1, F_, H, p + "ffn1.weight", Mc),
-                             (dh1m, rw.ctx, H, H, p + "o.weight", Mc)]
+        return ac.dh1_full, wg
 
     def encoder_backward(self, dx_top, grad_ready=None, inject=None):
         """dx_top bf16 [Mp,H] = d loss / d last hidden state; accumulates into arena.g.
@@ -788,13 +824,13 @@ class Tagger:
             ops.gather_rows(dx_top, self._rows_saved[0].row_ids, out=self._rows_saved[0].dx)
         dx = dx_top
         pending = []
-        dropping = any(d[1][1] for d in d_layers)
-        dhm_ring, dh1m_ring = ac.drop_buffers() if dropping else (ac.dh, ac.dh1)
+        if any(d[1][1] for d in d_layers):
+            ac.drop_buffers()
         # DEFER_REDUCE_MAX_TOKENS: below it every LayerNorm backward keeps its partial column sums in a workspace of its own and the
         # FFN-up bias gradients their epilogue lines; both are reduced for the whole pass at its end (ops.ln_colreduce_batched /
         # colsum_rows_f32_batched) instead of by 3 L launches of ~4.7 us
         defer = Mp <= self.DEFER_REDUCE_MAX_TOKENS and ops.HBM_HOOK is None
-        ln_items, cs_items, defer_ln, ln_blocks = [], [], None, 0
+        ln_items, cs_items, defer_ln, ln_blocks, deferral = [], [], None, 0, None
         dx_slabs = None     # (split-K slabs, slices, residual) standing in for `dx` when the producing GEMM left its fold to LN2 backward
         if defer:
             ln_blocks = ops.ln_bwd_blocks(Mp)
@@ -802,62 +838,21 @@ class Tagger:
                 ac.defer_ln_ws = torch.empty((2 * L + 1, ln_blocks * 3 * H), dtype=F32, device=self.device)
                 ac.colsum_ws_all = torch.empty((L, 2 * (Mp // 128), F_), dtype=F32, device=self.device)
             defer_ln = ac.defer_ln_ws
+            deferral = (defer_ln, ac.colsum_ws_all, ln_items, cs_items, ln_blocks)
         for l in range(L - 1, -1, -1):
             p = "l%d." % l
-            r = l % WGRAD_GROUP
-            dh, dh1, dpre, dqkv = ac.dh[r], ac.dh1[r], ac.dpre[r], ac.dqkv[r]
-            d_att, d_o, d_f = d_layers[l]
+            dqkv = ac.dqkv[l % WGRAD_GROUP]
             if rows and l == L - 1:
                 # the last layer ran on the head's rows only: its sub-layers' backward on the compact rows -> the full dqkv, dh1
                 # at the head's rows of a zero buffer, and three weight-gradient problems whose reduction runs over Mc rows
                 dh1, wg = self._last_layer_rows_backward(ac, l, maskbias, d_layers[l], dqkv)
             else:
-                # with hidden dropout the sub-layer GEMMs see dY = mask * dh (dhm / dh1m); the residual branch keeps dh / dh1
-                dhm = dhm_ring[r] if d_f[1] else dh
-                dh1m = dh1m_ring[r] if d_o[1] else dh1
-                # LN2 backward; fused: d ffn2.bias = column sums of dh
-                ops.ln_bwd(dx, ac.h2[l], ac.st2[l][0], ac.st2[l][1], a.param(p + "ln2.g"), dh, a.grad(p + "ln2.g"),
-                           a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), dhm=dhm if d_f[1] else None, drop=d_f,
-                           defer_ws=defer_ln[2 * l + 1] if defer else None, dy_slabs=dx_slabs)
-                dx_slabs = None
-                if defer:
-                    ln_items.append((defer_ln[2 * l + 1], a.grad(p + "ln2.g"), a.grad(p + "ln2.b"), a.grad(p + "ffn2.bias"), ln_blocks))
-                # FFN down dgrad: dpre = (dh W2) * gelu'(pre)   (the derivative itself was saved by the forward epilogue)
-                # (its column sums = d ffn1.bias are accumulated by the same epilogue when the 256^2 kernel runs)
-                fused = ops.uses_256(Mp, F_, occupancy=True)
-                if fused:
-                    # column sums (= d ffn1.bias) leave the epilogue as plain stores into a [2 * Mp/256, F] workspace, folded by a
-                    # small reduce kernel: per-tile atomics onto the same 4096 addresses were what made this the slowest GEMM
-                    if ac.colsum_ws is None:
-                        ac.colsum_ws = torch.empty((2 * (Mp // 128), F_), dtype=F32, device=self.device)
-                    # ops.gemm reports the tile height of the kernel that ran (256 under dynamic tile draw, the static kernel's pick --
-                    # also when the scheduler ring is used up -- otherwise): it decides how many workspace lines hold partial sums
-                    cws = ac.colsum_ws_all[l] if defer else ac.colsum_ws
-                    trows = ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l],
-                                     epi=EPI_DGELU | EPI_COLSUM | EPI_COLSUM_WS, colsum=cws, occupancy=True)
-                    if defer and 2 * (Mp // trows) <= 64:
-                        cs_items.append((cws, a.grad(p + "ffn1.bias"), 2 * (Mp // trows)))
-                    else:
-                        ops.colsum_rows_f32(cws, 2 * (Mp // trows), a.grad(p + "ffn1.bias"))
-                else:
-                    ops.gemm(GEMM_NN, dhm, a.bf(p + "ffn2.weight"), Mp, F_, H, C=dpre, aux=ac.dact[l], epi=EPI_DGELU, occupancy=True)
-                    ops.colsum(dpre, a.grad(p + "ffn1.bias"))
-                dx1_slabs = self._long_k_gemm(GEMM_NN, dpre, a.bf(p + "ffn1.weight"), Mp, H, F_, ac.dx1, ac, addend=dh, finish=False)
-                if dx1_slabs is not None:
-                    dx1_slabs = (dx1_slabs[0], dx1_slabs[1], dh)
-                # LN1 backward; fused: d o.bias
-                ops.ln_bwd(ac.dx1, ac.h1[l], ac.st1[l][0], ac.st1[l][1], a.param(p + "ln1.g"), dh1, a.grad(p + "ln1.g"),
-                           a.grad(p + "ln1.b"), a.grad(p + "o.bias"), dhm=dh1m if d_o[1] else None, drop=d_o,
-                           defer_ws=defer_ln[2 * l] if defer else None, dy_slabs=dx1_slabs)
-                if defer:
-                    ln_items.append((defer_ln[2 * l], a.grad(p + "ln1.g"), a.grad(p + "ln1.b"), a.grad(p + "o.bias"), ln_blocks))
-                # attention output projection
-                ops.gemm(GEMM_NN, dh1m, a.bf(p + "o.weight"), Mp, H, H, C=ac.dctx, occupancy=True)
+                v = ac.layers[l]
+                wg = self._sublayers_backward(v, l, dx, d_layers[l], dx_slabs, deferral)
+                dx_slabs, dh1 = None, v.dh1
                 # attention core (+ d qkv.bias = column sums of dqkv, accumulated inside the kernels)
-                ops.attn_bwd(ac.qkv[l], ac.ctx[l], ac.dctx, maskbias, ac.lse[l], ac.dws, dqkv, B, S, H, A, drop=d_att,
+                ops.attn_bwd(ac.qkv[l], v.ctx, v.dctx, maskbias, ac.lse[l], ac.dws, dqkv, B, S, H, A, drop=d_layers[l][0],
                              dbias=a.grad(p + "qkv.bias"), ctx_lo=ac.ctx_lo[l] if self.ATTN_RESIDUAL else None)
-                wg = [(dhm, ac.act[l], H, F_, p + "ffn2.weight", Mp), (dpre, ac.x1[l], F_, H, p + "ffn1.weight", Mp),
-                      (dh1m, ac.ctx[l], H, H, p + "o.weight", Mp)]
             # QKV projection
             # (the next layer's LN2 backward folds this GEMM's slabs itself -- the first launch of that layer, before anything
             #  else writes the slab buffer; layer 0's gradient goes to the embedding LayerNorm as bf16)
