@@ -394,6 +394,28 @@ int kbner_lstm_step(const kbner_bf16* gx, int ld_gx, const int* gxi, const kbner
  * blocks are not equidistant run as ONE group; h bf16 [2, ndir, B, Hp] ping-pong (h[0] = h_0, result in h[steps & 1]). */
 int kbner_lstm_seq(const kbner_bf16* gx, int ld_gx, const int* gxi, const kbner_bf16* whh, kbner_bf16* h, float* c, kbner_bf16* out,
                    int ldo, const int* out_col, const int* outi, int steps, int B, int Hp, int ndir, void* stream);
+/* Training of the BiLSTM head on frozen features (csrc/lstm_train.hip; the reference trains torch.nn.LSTM by autograd,
+ * sequence_tagger_model.py:969-994 under finetune_trainer.py:1000-1020).  TRAINING CONTRACT of the row tables: prefix-active (every
+ * (direction, sequence) active for steps 0 .. len - 1, -1 after) and no (direction, gx row) consumed twice; h_0 = c_0 = 0.  The
+ * tables live in device memory: the caller checks (kbner.stack.check_prefix_active).
+ * kbner_lstm_seq_train: kbner_lstm_seq (h, c and out bit-equal to it) that also stores, for an active (d, b) at step s with
+ * r = gxi[s, d, b], into direction d's columns of row r: the post-activation gates (gates bf16 [rows_gx, ndir * 4Hp], i | f | g | o),
+ * c_t (cs f32 [rows_gx, ndir * Hp]) and the h_{t-1} row it multiplied (hprev bf16 [rows_gx, ndir * Hp]). */
+int kbner_lstm_seq_train(const kbner_bf16* gx, int ld_gx, const int* gxi, const kbner_bf16* whh, kbner_bf16* h, float* c,
+                         kbner_bf16* out, int ldo, const int* out_col, const int* outi, int steps, int B, int Hp, int ndir,
+                         kbner_bf16* gates, float* cs, kbner_bf16* hprev, void* stream);
+/* Back-propagation through that recurrence: one launch per time step, last step first, enqueued back to back.  For an active (d, b)
+ * at step s with r = gxi[s], nx = gxi[s + 1] (-1 past the end or when finished), pv = gxi[s - 1] (-1 at s = 0):
+ *   dh = dout[outi[s], out_col[d] + :] (0 where outi < 0) + (nx >= 0 ? dgx[nx, d-block] . Whh_d : 0)
+ *   t = tanh(c[r]) ; c_prev = pv >= 0 ? c[pv] : 0 ; dc = dc_carry + dh o (1 - t^2)
+ *   di = dc g i (1 - i) ; df = dc c_prev f (1 - f) ; dg = dc i (1 - g^2) ; do = dh t o (1 - o)
+ *   dc_carry = dc f ; dgx[r, d-block] = (di, df, dg, do) in bf16
+ * whht bf16 [ndir, Hp, 4Hp] (Whh transposed); dc_carry f32 [ndir, B, Hp], zero on entry; dgx bf16 [rows_gx, ld_dgx]: rows no step
+ * consumes are untouched (the caller zero-fills them), finished sequences touch nothing.  Hp % 64 == 0, ldo % 4 == 0,
+ * ld_dgx % 8 == 0, ld_dgx >= ndir * 4Hp. */
+int kbner_lstm_seq_bwd(const kbner_bf16* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const kbner_bf16* whht,
+                       const kbner_bf16* gates, const float* cs, float* dc_carry, kbner_bf16* dgx, int ld_dgx, int steps, int B,
+                       int Hp, int ndir, void* stream);
 
 /* ---------------- optimiser (transformers==3.0.0 AdamW + clip_grad_norm_, finetune_trainer.py:1010,1018) ------------- */
 int kbner_sqnorm_ws_floats(void);
@@ -401,6 +423,10 @@ int kbner_grad_sqnorm(const float* g, size_t n, float* ws, float* out, int accum
 int kbner_adamw_hf(float* p, float* g, float* m, float* v, kbner_bf16* shadow, size_t n, size_t n_shadow, float step_size,
                    float lr_wd, float b1, float b2, float eps, const float* gnorm_sq, float max_norm, float grad_scale,
                    int zero_grad, void* stream);
+/* Plain SGD, p -= lr * clip * grad_scale * g with the clip rule, bf16 shadow write and gradient zeroing of kbner_adamw_hf
+   (torch.optim.SGD as the reference's ModelFinetuner builds it for `optimizer: SGD`, finetune_trainer.py:552-571; shadow may be NULL). */
+int kbner_sgd(float* p, float* g, kbner_bf16* shadow, size_t n, size_t n_shadow, float lr, const float* gnorm_sq, float max_norm,
+              float grad_scale, int zero_grad, void* stream);
 /* The same update restricted to the rows of an embedding table that have ever received a gradient (flags u8[rows], set by
    kbner_mark_rows from the looked-up ids): an unflagged row has g = m = v = 0, so with weight decay 0 HF AdamW leaves it
    unchanged and it is not read.  (The reference's dense optimizer.step() walks all 250 002 rows of XLM-R's word embedding,

@@ -16,14 +16,9 @@
 // backward direction are expressed by per-step row tables: which pre-activation row each sequence consumes at this step
 // (-1 = the sequence is finished: state carried unchanged) and where its h_t goes in the output (-1 = not needed).
 #include "common.h"
+#include "lstm_act.h"
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-static __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
-static __device__ __forceinline__ float tanh_f(float x) {
-  // tanh(x) = 1 - 2 / (exp(2x) + 1): exact to fp32 rounding, saturates cleanly at +-1 (exp overflow -> inf -> 1 - 0)
-  return 1.0f - 2.0f / (__expf(2.0f * x) + 1.0f);
-}
 
 // grid (Hp / 16, ceil(B / 16), ndir); block 64.
 // gx   bf16 [rows_gx, ld_gx]  : pre-activations Wih x + bih + bhh, direction d at column d * 4 * Hp, gate q at + q * Hp

@@ -73,6 +73,33 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   }
 }
 
+// Plain SGD over a flat arena (torch.optim.SGD without momentum or weight decay: the optimizer Flair-style BiLSTM taggers and the
+// shipped ACE YAML train with): p -= lr * (g * gs), gs as in adamw_kernel (clip coefficient from device memory), the same bf16
+// shadow write and gradient zeroing.
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ g, bf16_t* __restrict__ shadow, size_t n,
+                                                  size_t n_shadow, float lr, const float* __restrict__ gnorm_sq, float max_norm,
+                                                  float grad_scale, int zero_grad) {
+  const float gs = clipped_grad_scale(gnorm_sq, max_norm, grad_scale);
+  const size_t n4 = n / 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    pp.x -= lr * (gg.x * gs);
+    pp.y -= lr * (gg.y * gs);
+    pp.z -= lr * (gg.z * gs);
+    pp.w -= lr * (gg.w * gs);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (shadow && (i * 4 + 3) < n_shadow) {
+      uint2 u;
+      u.x = pack2bf(pp.x, pp.y);
+      u.y = pack2bf(pp.z, pp.w);
+      reinterpret_cast<uint2*>(shadow)[i] = u;
+    }
+  }
+}
+
 // Row-gated variants for an EMBEDDING table [rows, width]: a row whose flag is 0 has never received a gradient, so its g, m and
 // v are exactly 0 and (weight decay 0) the AdamW update leaves p unchanged: the row is not read at all.  XLM-R's word embedding
 // is 46 % of the parameters and a corpus touches a small part of its 250 002 rows, so with the YAMLs' 4 sentences per optimiser
@@ -388,6 +415,18 @@ int kbner_adamw_hf(float* p, float* g, float* m, float* v, bf16_t* shadow, size_
   if (n == 0) return 0;
   hipLaunchKernelGGL(adamw_kernel, dim3(flat4_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n, n_shadow,
                      step_size, lr_wd, b1, b2, eps, gnorm_sq, max_norm, grad_scale, zero_grad);
+  KBNER_LAUNCH_RET();
+}
+
+// SGD on a flat arena: p -= lr * clip * grad_scale * g (clip as kbner_adamw_hf: max_norm / (sqrt(*gnorm_sq) * grad_scale + 1e-6) where
+// that is below 1; gnorm_sq NULL: no clipping).  n % 4 == 0, n_shadow % 4 == 0, n_shadow <= n; shadow may be NULL.
+int kbner_sgd(float* p, float* g, bf16_t* shadow, size_t n, size_t n_shadow, float lr, const float* gnorm_sq, float max_norm,
+              float grad_scale, int zero_grad, void* stream) {
+  KBNER_CHECK_ARG(p != nullptr && g != nullptr);
+  KBNER_CHECK_ARG(n % 4 == 0 && n_shadow % 4 == 0 && n_shadow <= n);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(sgd_kernel, dim3(flat4_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, p, g, shadow, n, n_shadow, lr, gnorm_sq,
+                     max_norm, grad_scale, zero_grad);
   KBNER_LAUNCH_RET();
 }
 

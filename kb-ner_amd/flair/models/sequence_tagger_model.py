@@ -179,9 +179,12 @@ class SequenceTagger(flair.nn.Model):
         self.engine = None
         self.stack_head = None
         if self.use_rnn:
-            # BASELINE config 5: frozen stacked embeddings -> BiLSTM -> linear -> CRF, inference only (kbner.stack)
-            if dropout:
-                raise NotImplementedError("dropout > 0 on the tagger head is not implemented")
+            # BASELINE config 5: frozen stacked embeddings -> BiLSTM -> linear -> CRF (kbner.stack); the head trains on the frozen
+            # features (forward_backward), with the reference's dropouts before and after the BiLSTM (:959-964, 988-994)
+            for k, p in (("dropout", dropout), ("word_dropout", word_dropout), ("locked_dropout", locked_dropout)):
+                if not 0.0 <= float(p or 0.0) < 1.0:
+                    raise ValueError("%s must be in [0, 1) (got %r)" % (k, p))
+            self.use_dropout, self.use_locked_dropout = float(dropout or 0.0), float(locked_dropout or 0.0)
             self._build_stack()
         else:
             if hasattr(embeddings, "embeddings") and len(embeddings.embeddings) != 1:
@@ -244,7 +247,7 @@ class SequenceTagger(flair.nn.Model):
         if getattr(self, "_emb", None) is not None and getattr(self._emb, "model", None) is not None:
             self._emb.model.source = None
 
-    # ------------------------------------------------------------------ config 5: frozen stack + BiLSTM (inference)
+    # ------------------------------------------------------------------ config 5: frozen stack + BiLSTM
     def _build_stack(self):
         """BiLSTM(sum of embedding widths -> hidden_size, bidirectional) + linear(2 * hidden -> T) + transitions, initialised
         like the reference's torch modules (sequence_tagger_model.py:324-357,385-388,402-410); `load_stack_state` overwrites
@@ -284,10 +287,49 @@ class SequenceTagger(flair.nn.Model):
                              "linear.weight": torch.as_tensor(state["linear.weight"]).detach().float().cpu(),
                              "linear.bias": torch.as_tensor(state["linear.bias"]).detach().float().cpu(),
                              "transitions": torch.as_tensor(state["transitions"]).detach().float().cpu()}
-        st = self._stack_state
+        st = self.__dict__["_stack_state_host"]
+        head = getattr(self, "stack_head", None)
+        if head is not None and head.arena is not None:
+            # a trainable tagger: the arena is refreshed in place and the optimizer moments of the old weights are dropped
+            head.load_state(st)
+            if getattr(self, "stack_optimizer", None) is not None:
+                self.stack_optimizer.reset()
+            return
         self.stack_head = K.BiLSTMHead(st["rnn"], st["linear.weight"], st["linear.bias"], self._stack_blocks, self.hidden_size,
                                        flair.device)
         self._transitions = st["transitions"].to(flair.device).contiguous()
+
+    @property
+    def _stack_state(self):
+        """the stack's weights in the reference's layout; of a trainable tagger: read from the parameter arena"""
+        head = getattr(self, "stack_head", None)
+        if head is not None and head.arena is not None:
+            return head.state()
+        return self.__dict__["_stack_state_host"]
+
+    @_stack_state.setter
+    def _stack_state(self, st):
+        self.__dict__["_stack_state_host"] = st
+
+    def enable_stack_training(self):
+        """Make the BiLSTM -> linear -> CRF head trainable (kbner.stack.BiLSTMHead.enable_training: parameter arena, gradient
+        buffer, bf16 shadow).  The embeddings stay constants: one with fine_tune: true is refused."""
+        if not self.use_rnn:
+            raise ValueError("enable_stack_training() belongs to the stacked tagger (use_rnn: true)")
+        head = self.stack_head
+        if head.arena is not None:
+            return head
+        for e in self._stack_embs:
+            if getattr(e, "fine_tune", False):
+                raise NotImplementedError("embedding %s has fine_tune: true: the stacked tagger (use_rnn: true) trains its BiLSTM head "
+                                          "on frozen features, no gradient flows into an embedding" % e.name)
+        st = self.__dict__["_stack_state_host"]
+        head.enable_training(st["rnn"], st["linear.weight"], st["linear.bias"], st["transitions"])
+        head.dropout, head.locked_dropout = self.use_dropout, self.use_locked_dropout
+        head.word_dropout = float(self.use_word_dropout or 0.0)
+        head.seed_dropout(int(torch.initial_seed() % (2 ** 31)))
+        head.train(self.training)
+        return head
 
     def _encoder_for(self, emb):
         """frozen encoder of one TransformerWordEmbeddings on the HIP engine (weights loaded once, no gradient arenas)"""
@@ -381,15 +423,18 @@ class SequenceTagger(flair.nn.Model):
     def train(self, mode: bool = True):
         """model.train() (finetune_trainer.py:938) switches the HF dropout sites and the tagger's WordDropout on; eval() off"""
         super().train(mode)
-        if getattr(self, "use_rnn", False) and mode:
-            log.warning("the BiLSTM / stacked tagger is inference-only here: train() mode has no effect")
+        if getattr(self, "stack_head", None) is not None:
+            self.stack_head.train(mode)     # the head's dropouts (a head that was not made trainable stays in inference mode)
         if getattr(self, "engine", None) is not None:
             self.engine.train(bool(mode) and bool(getattr(self._emb, "fine_tune", True)))
         return self
 
     @property
     def transitions(self):
-        return self._transitions if self.engine is None else self.engine.arena.param("transitions")
+        if self.engine is None:
+            head = self.stack_head
+            return self._transitions if head.arena is None else head.param("transitions")
+        return self.engine.arena.param("transitions")
 
     @property
     def linear(self):
@@ -407,7 +452,7 @@ class SequenceTagger(flair.nn.Model):
     def named_parameters(self, prefix="", recurse=True):
         """(name, tensor view) with the reference's naming: `transitions`, `linear.*`, `embeddings.list_embedding_0.model.<hf>`"""
         if self.engine is None:
-            yield "transitions", self._transitions
+            yield "transitions", self.transitions
             yield "linear.weight", self._stack_state["linear.weight"]
             yield "linear.bias", self._stack_state["linear.bias"]
             for k, v in self._stack_state["rnn"].items():
@@ -425,6 +470,8 @@ class SequenceTagger(flair.nn.Model):
             yield p
 
     def zero_grad(self, set_to_none=False):
+        if getattr(self, "stack_head", None) is not None and self.stack_head.arena is not None:
+            self.stack_head.g.zero_()
         if self.engine is not None and self.engine.arena.g is not None:    # None: a teacher after drop_gradients()
             self.engine.arena.g.zero_()
             self.engine.arena.wgrad_stale = False
@@ -492,7 +539,7 @@ class SequenceTagger(flair.nn.Model):
         tempered posteriors of its CRF are pulled towards those of the context view just computed (constant), each sentence
         weighted by `weights`.  Returns the NLL term + the distillation term (both weighted as given) as one 0-d tensor."""
         if self.use_rnn:
-            raise NotImplementedError("training the BiLSTM / stacked-embedding tagger (ACE) is out of scope: config 5 is inference-only")
+            return self._stack_forward_backward(data_points, loss_scale, sentence_weights, grad_ready, multi_view, distill_interpolation)
         self.embeddings.embed(data_points)
         hb, db = self._device_batch(data_points)
         self._last = (hb, db)
@@ -539,6 +586,33 @@ class SequenceTagger(flair.nn.Model):
         store_embeddings(orig, "none")
         self.last_loss_parts = (loss, kd)   # (weighted NLL of the context view, weighted distillation term): 0-d device tensors
         return loss + kd
+
+    def _stack_forward_backward(self, data_points, loss_scale, sentence_weights, grad_ready, multi_view, distill_interpolation):
+        """the stacked tagger's step: the feature producers forward only (constants), then BiLSTMHead.loss_backward"""
+        for name, v in (("multi_view", multi_view), ("distill_interpolation", distill_interpolation), ("grad_ready", grad_ready)):
+            if v is not None:
+                raise NotImplementedError("forward_backward(%s=...) is not implemented for the stacked tagger (use_rnn: true): one "
+                                          "process trains its BiLSTM head on frozen features, without distillation" % name)
+        from kbner import batch as kb
+        if isinstance(data_points, Sentence):
+            data_points = [data_points]
+        head = self.enable_stack_training()
+        X, lengths, B, n = self._stack_input(data_points)
+        tags = np.zeros((B, n), np.int64)
+        for b, s in enumerate(data_points):
+            t = getattr(s, self.tag_type + "_tags", None)
+            if t is not None:
+                t = np.asarray(t)
+                tags[b, :min(n, len(t))] = t[:n]
+            else:
+                tags[b, :len(s)] = [self.tag_dictionary.get_idx_for_item(tok.get_tag(self.tag_type).value) for tok in s]
+        hb = kb.assemble(np.zeros((B, 1), np.int64), np.ones((B, 1), np.int64), np.full((B, n), -1, np.int64), tags, lengths, self.x_idx)
+        db = kb.to_device(hb, flair.device)
+        self._last = (hb, db)
+        self.mask = db["keep_f"]
+        loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale, weights=sentence_weights)
+        self.last_loss_parts = (loss, None)
+        return loss
 
     # ------------------------------------------------------------------ teacher-student knowledge distillation
     def _kd_suppress(self):

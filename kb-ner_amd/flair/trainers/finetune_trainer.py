@@ -60,6 +60,9 @@ class ModelFinetuner:
                                           "distill_posterior / distill_exact / distill_emission")
             for teacher in teachers:
                 teacher.eval()
+        # the trainer block's `optimizer` name (finetune_trainer.py:552-571 builds it from the YAML): read by the stacked tagger's
+        # loop, which trains with AdamW or SGD; the fine-tuning loop is HF AdamW whatever it says
+        self.optimizer_name = optimizer if isinstance(optimizer, str) else "AdamW"
         self.optimizer_state = optimizer_state     # checkpoint resume (finetune_trainer.py:573,690)
         self.scheduler_state = scheduler_state
         self.corpus = corpus
@@ -289,6 +292,12 @@ class ModelFinetuner:
         differ (WordDropout positions are shared by the fused batch), nothing else does."""
         from kbner import dp
         from kbner.engine import FusedAdamW
+        if getattr(self.model, "use_rnn", False):
+            # the stacked tagger trains its BiLSTM -> linear -> CRF head on frozen features: a loop of its own (below)
+            a = dict(locals())
+            for k in ("self", "kwargs", "dp", "FusedAdamW", "base_path"):
+                a.pop(k)
+            return self._train_stack(Path(base_path), a, kwargs)
         _warn_unknown("ModelFinetuner.train", kwargs)
         for flag, on in (("use_amp", use_amp), ("use_autocast", use_autocast), ("rootschedule", rootschedule),
                          ("freezing", freezing), ("use_unlabeled_data", use_unlabeled_data),
@@ -566,6 +575,135 @@ class ModelFinetuner:
         return {"test_score": final_score, "dev_score_history": dev_score_history, "train_loss_history": train_loss_history,
                 "dev_loss_history": dev_loss_history}
 
+    def _train_stack(self, base_path, a, kwargs):
+        """ModelFinetuner.train for a `use_rnn: true` model (frozen embeddings -> BiLSTM -> linear -> CRF).  One process.  Walks the
+        ColumnDataLoader batches, `gradient_accumulation_steps` micro-batches of forward_backward per optimizer step
+        (kbner.stack.StackOptimizer: AdamW, the default, or SGD by the trainer block's `optimizer`; `linear.*` at learning_rate,
+        `rnn.*` and `transitions` at learning_rate * lr_rate, finetune_trainer.py:552-571), evaluates on dev after every epoch and
+        writes the best dev score's weights to `stack-model.pt` (the reference-layout dict load_stack_state takes), training.log and
+        loss.tsv as the fine-tuning loop does.  Schedule: fine_tune_mode -> linear decay with warm-up (:672-688); otherwise the
+        plateau rule the reference uses off the fine-tune path (:1362-1390): lr *= anneal_factor after `patience` epochs without a
+        better dev score, stop below min_learning_rate."""
+        from kbner import dp
+        from kbner.stack import StackOptimizer
+        _warn_unknown("ModelFinetuner.train", kwargs)
+        if dp.world_size() > 1:
+            raise NotImplementedError("WORLD_SIZE > 1: the stacked tagger (use_rnn: true) trains in one process")
+        if self.distill_mode:
+            raise NotImplementedError("distill_mode: knowledge distillation of the stacked tagger (use_rnn: true) is not implemented")
+        if a["checkpoint"] or self.optimizer_state is not None:
+            raise NotImplementedError("checkpoint: resuming the stacked tagger (use_rnn: true) is not implemented")
+        if a["train_with_dev"]:
+            raise NotImplementedError("train_with_dev: the stacked tagger (use_rnn: true) selects stack-model.pt by the dev score")
+        for flag in ("use_amp", "use_autocast", "rootschedule", "freezing", "use_unlabeled_data", "unlabeled_data_for_zeroshot",
+                     "gold_reward", "language_attention_warmup", "language_attention_warmup_and_fix"):
+            if a[flag]:
+                raise NotImplementedError("train(%s=...) selects a path outside the stacked tagger's training loop" % flag)
+        name = {"adamw": "AdamW", "sgd": "SGD"}.get(str(self.optimizer_name).lower(), str(self.optimizer_name))
+        model = self.model
+        base_path.mkdir(parents=True, exist_ok=True)
+        handler = add_file_handler(log, base_path / "training.log")
+        lr0, mbs, accum = float(a["learning_rate"]), int(a["mini_batch_size"]), max(1, int(a["gradient_accumulation_steps"]))
+        eval_bs = a["eval_mini_batch_size"] or max(mbs, 32 if self.sentence_level_batch else mbs)
+        train_data = [s for ds in self.corpus.train_list for s in ds]
+        loader = ColumnDataLoader(train_data, mbs, a["shuffle"], use_bert=self.use_bert, tokenizer=self.bert_tokenizer, model=model,
+                                  sentence_level_batch=self.sentence_level_batch, sort_data=a["sort_data"])
+        loader.assign_tags(model.tag_type, model.tag_dictionary)
+        dev_loaders = []
+        for ds in self.corpus.dev_list:
+            dl = ColumnDataLoader(list(ds), eval_bs, False, sort_data=a["sort_data"], model=model, sentence_level_batch=self.sentence_level_batch)
+            dl.assign_tags(model.tag_type, model.tag_dictionary)
+            dev_loaders.append(dl)
+        if not dev_loaders or not any(len(d) for d in dev_loaders):
+            raise NotImplementedError("the stacked tagger (use_rnn: true) needs a dev set to select stack-model.pt by")
+        head = model.enable_stack_training()
+        opt = StackOptimizer(head, name=name, lr=lr0, lr_rate=float(a["lr_rate"]), max_norm=5.0)
+        model.stack_optimizer = self.optimizer = opt
+        steps_epoch = (len(loader) + accum - 1) // accum
+        t_total = steps_epoch * int(a["max_epochs"])
+        warmup = steps_epoch * int(a["warmup_epochs"]) if a["use_warmup"] else int(a["warmup_steps"])
+        linear = bool(a["fine_tune_mode"])
+
+        def linear_scale(t):
+            if t < warmup:
+                return float(t) / float(max(1, warmup))
+            return max(0.0, float(t_total - t) / float(max(1, t_total - warmup)))
+        plateau = 1.0
+        log_line(log)
+        log.info('Model: "frozen stacked embeddings + BiLSTM + linear + CRF on kbner HIP engine", tags=%d, optimizer %s', len(model.tag_dictionary), name)
+        log.info('Parameters: learning_rate "%s", lr_rate "%s", mini_batch_size "%s", accumulate "%s", max_epochs "%s", schedule "%s"',
+                 lr0, a["lr_rate"], mbs, accum, a["max_epochs"], "linear, warmup %d" % warmup if linear else "plateau")
+        log_line(log)
+        loss_txt = init_output_file(base_path, "loss.tsv")
+        with open(loss_txt, "a") as f:
+            f.write("EPOCH\tTIMESTAMP\tLEARNING_RATE\tTRAIN_LOSS\tDEV_LOSS\tDEV_F1\tDEV_MACRO_F1\n")
+        rng = random.Random(20220711)
+        order = list(range(len(loader)))
+        best_score, bad_epochs = -1.0, 0
+        dev_score_history, dev_loss_history, train_loss_history = [], [], []
+        hook = getattr(self, "stack_step_hook", None)     # tests: called after every optimizer step with (its batches, their losses)
+        try:
+            for epoch in range(self.epoch, int(a["max_epochs"])):
+                if a["shuffle"]:
+                    rng.shuffle(order)
+                model.train()
+                tot, cnt, t_ep, seen = 0.0, 0, time.time(), 0
+                for g0 in range(0, len(order), accum):
+                    group = order[g0:g0 + accum]
+                    losses = []
+                    for bi in group:
+                        batch = loader[bi]
+                        losses.append(model.forward_backward(batch, loss_scale=1.0 / len(group)))
+                        seen += len(batch)
+                        store_embeddings(batch, "none")
+                    opt.lr_scale = linear_scale(opt.t) if linear else plateau
+                    opt.step()
+                    if hook is not None:
+                        hook([loader[bi] for bi in group], losses)
+                    tot += float(sum(losses)) / len(group)
+                    cnt += 1
+                train_loss = tot / max(cnt, 1)
+                train_loss_history.append(train_loss)
+                model.trained_epochs = epoch + 1
+                model.eval()
+                lr_now = lr0 * (linear_scale(opt.t) if linear else plateau)
+                log_line(log)
+                log.info("EPOCH %d done: loss %.4f - lr %.2e - %.1f sentences/sec", epoch + 1, train_loss, lr_now, seen / max(time.time() - t_ep, 1e-9))
+                f1s, dls = [], []
+                for dname, dl in zip(getattr(self.corpus, "targets", ["dev"]), dev_loaders):
+                    res, dl_loss = model.evaluate(dl, embeddings_storage_mode="none")
+                    log.info("%s DEV : loss %.4f - f1 %.4f - macro %.4f", dname, dl_loss, res.main_score, res.macro_score)
+                    f1s.append((res.macro_score if a["select_model_by_macro"] else res.main_score) * 100)
+                    dls.append(dl_loss)
+                score = sum(f1s) / len(f1s)
+                dev_score_history.append(score)
+                dev_loss_history.append(sum(dls) / len(dls))
+                with open(loss_txt, "a") as f:
+                    f.write("%d\t%s\t%.3e\t%.6f\t%s\t%s\t_\n" % (epoch + 1, time.strftime("%H:%M:%S"), lr_now, train_loss, dev_loss_history[-1], score))
+                if score > best_score:
+                    best_score, bad_epochs = score, 0
+                else:
+                    bad_epochs += 1
+                if score == best_score:
+                    log.info("==================Saving the current best model: %s==================", score)
+                    torch.save(model._stack_state, str(base_path / "stack-model.pt"))
+                if not linear and bad_epochs > int(a["patience"]):
+                    plateau *= float(a["anneal_factor"])
+                    bad_epochs = 0
+                    log.info("no better dev score for %d epochs: learning rate -> %.3e", int(a["patience"]) + 1, lr0 * plateau)
+                    if lr0 * plateau < float(a["min_learning_rate"]):
+                        log.info("learning rate below min_learning_rate: stopping")
+                        break
+        except KeyboardInterrupt:
+            log_line(log)
+            log.info("Exiting from training early.")
+        final_score = 0.0
+        if self.corpus.test is not None and len(self.corpus.test) > 0:
+            final_score = self.final_test(base_path, eval_bs, quiet_mode=False)
+        log.removeHandler(handler)
+        return {"test_score": final_score, "dev_score_history": dev_score_history, "train_loss_history": train_loss_history,
+                "dev_loss_history": dev_loss_history}
+
     def save_finetuned_embedding(self, base_path):
         """write `<base_path>/<basename of the embedding dir>/` with tokenizer + current encoder weights, the directory the
         next fine-tuning stage's YAML names (finetune_trainer.py:1289-1312)"""
@@ -583,6 +721,9 @@ class ModelFinetuner:
         base_path = Path(base_path)
         log_line(log)
         self.model.eval()
+        if getattr(self.model, "use_rnn", False) and (base_path / "stack-model.pt").exists() and type(self).__name__ == "ModelFinetuner":
+            self.model.load_stack_state(torch.load(str(base_path / "stack-model.pt"), map_location="cpu", weights_only=False))
+            log.info("Testing using stack-model.pt ...")
         for name in ("best-model.pt", "final-model.pt"):
             if (base_path / name).exists() and getattr(self.model, "engine", None) is not None:
                 state = torch.load(str(base_path / name), map_location="cpu", weights_only=False)

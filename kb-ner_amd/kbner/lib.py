@@ -83,6 +83,8 @@ SIGNATURES = {
     "kbner_rows_drop_add": (c_int, [P, c_int, P, P, P, P, c_int, c_int, U32, U32, P]),
     "kbner_lstm_step": (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, P, c_int, c_int, c_int, P]),
     "kbner_lstm_seq": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    "kbner_lstm_seq_train": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "kbner_lstm_seq_bwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "kbner_sqnorm_ws_floats": (c_int, []),
     "kbner_grad_sqnorm": (c_int, [P, c_size_t, P, P, c_int, P]),
     "kbner_mark_rows": (c_int, [P, c_int, P, c_int, P]),
@@ -93,6 +95,7 @@ SIGNATURES = {
     "kbner_adamw_rows_catchup": (c_int, [P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, P]),
     "kbner_adamw_hf": (c_int, [P, P, P, P, P, c_size_t, c_size_t, c_float, c_float, c_float, c_float, c_float, P, c_float,
                                c_float, c_int, P]),
+    "kbner_sgd": (c_int, [P, P, P, c_size_t, c_size_t, c_float, P, c_float, c_float, c_int, P]),
     "kbner_f32_to_bf16": (c_int, [P, P, c_size_t, P]),
     "kbner_bf16_to_f32": (c_int, [P, P, c_size_t, P]),
     "kbner_wdiff_sum": (c_int, [P, P, P, c_int, P, P]),

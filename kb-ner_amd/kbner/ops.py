@@ -714,7 +714,7 @@ def rows_drop_add(y, row_ids, out, drop, bias=None, addend=None):
            int(drop[0]) & 0xFFFFFFFF, int(drop[1]), stream_ptr())
 
 
-# ---------------------------------------------------------------- LSTM (inference)
+# ---------------------------------------------------------------- LSTM (single step; the sequence entries: kbner/stack.py)
 def lstm_step(gx, gxi, whh, h_in, h_out, c, out, outi, out_dir_stride):
     """one time step for ndir directions: gx bf16 [rows, ndir*4*Hp]; gxi / outi i32 [ndir, B]; whh bf16 [ndir, 4Hp, Hp];
     h_in / h_out bf16 [ndir, B, Hp]; c f32 [ndir, B, Hp]; out bf16 [rows_out, ldo]"""
@@ -738,6 +738,13 @@ def adamw(p, g, m, v, shadow, n_shadow, step_size, lr_wd, b1, b2, eps, gnorm_sq,
     with _hbm_timed("adamw_kernel", 28 * p.numel()):
         L.call("kbner_adamw_hf", ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), p.numel(), n_shadow, step_size, lr_wd, b1, b2, eps,
                ptr(gnorm_sq), max_norm, grad_scale, 1 if zero_grad else 0, stream_ptr())
+
+
+def sgd(p, g, shadow, n_shadow, lr, gnorm_sq, max_norm, grad_scale, zero_grad=True):
+    """p -= lr * clip * grad_scale * g on a flat arena range (kbner_sgd: the clip rule, shadow write and zeroing of adamw)"""
+    _chk(p, F32, "p"); _chk(g, F32, "g")
+    L.call("kbner_sgd", ptr(p), ptr(g), ptr(shadow), p.numel(), n_shadow, lr, ptr(gnorm_sq), max_norm, grad_scale, 1 if zero_grad else 0,
+           stream_ptr())
 
 
 U8 = torch.uint8

@@ -1,4 +1,5 @@
-"""Inference engine of BASELINE config 5 (ACE-style stacked embeddings -> BiLSTM -> linear -> CRF Viterbi), all arithmetic in
+"""Engine of BASELINE config 5 (ACE-style stacked embeddings -> BiLSTM -> linear -> CRF): inference, and training of the BiLSTM
+-> linear -> CRF head on frozen features (BiLSTMHead.enable_training / loss_backward, StackOptimizer), all arithmetic in
 libkbner_hip.so.
 
 Reference path (restated): FastSequenceTagger.forward with `use_rnn` (flair/models/sequence_tagger_model.py:844-1052):
@@ -17,7 +18,7 @@ import torch
 
 from . import lib as L_
 from . import ops
-from .lib import EPI_BIAS, GEMM_NT
+from .lib import EPI_ATOMIC32, EPI_BIAS, GEMM_NT, GEMM_TN
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -69,6 +70,40 @@ class LSTMGroup:
                 out.shape[-1], L_.ptr(oc), L_.ptr(outi), steps, B, self.Hp, self.ndir, L_.stream_ptr())
         return h[steps & 1]
 
+    def whh_t(self):
+        """Whh of every direction transposed, bf16 [ndir, Hp, 4Hp]: what kbner_lstm_seq_bwd reads (made once per optimizer step)"""
+        return self.whh.transpose(1, 2).contiguous()
+
+    def run_train(self, gx, gxi_host, out, B, out_cols):
+        """The recurrence from h_0 = c_0 = 0 through kbner_lstm_seq_train.  gxi_host int32 [steps, ndir, B] (numpy; used as outi
+        too), checked against the training contract before upload.  -> the saved state for run_bwd."""
+        gxi_host = check_prefix_active(gxi_host, gx.shape[0], self.ndir, B)
+        if len(out_cols) != self.ndir or any(int(x) % 4 for x in out_cols):
+            raise L_.KbnerError("LSTM output column offsets: one per direction, each a multiple of 4")
+        steps, rows, Hp, nd = gxi_host.shape[0], gx.shape[0], self.Hp, self.ndir
+        tab = torch.from_numpy(gxi_host).to(self.device)
+        h = torch.zeros((2, nd, B, Hp), dtype=BF16, device=self.device)
+        c = torch.zeros((nd, B, Hp), dtype=F32, device=self.device)
+        oc = torch.tensor([int(x) for x in out_cols], dtype=I32, device=self.device)
+        # zero-filled: the weight-gradient GEMMs read every row, consumed or not
+        saved = dict(gates=torch.zeros((rows, nd * 4 * Hp), dtype=BF16, device=self.device),
+                     cs=torch.zeros((rows, nd * Hp), dtype=F32, device=self.device),
+                     hprev=torch.zeros((rows, nd * Hp), dtype=BF16, device=self.device), tab=tab, oc=oc, steps=steps, B=B)
+        L_.call("kbner_lstm_seq_train", L_.ptr(gx), gx.shape[-1], L_.ptr(tab), L_.ptr(self.whh), L_.ptr(h), L_.ptr(c), L_.ptr(out),
+                out.shape[-1], L_.ptr(oc), L_.ptr(tab), steps, B, Hp, nd, L_.ptr(saved["gates"]), L_.ptr(saved["cs"]),
+                L_.ptr(saved["hprev"]), L_.stream_ptr())
+        return saved
+
+    def run_bwd(self, dout, saved, whh_t):
+        """dout bf16 [rows_out, ld]: the gradient of run_train's `out` -> dgx bf16 [rows, ndir*4Hp] (zero where nothing was consumed)"""
+        rows, Hp, nd, B = saved["gates"].shape[0], self.Hp, self.ndir, saved["B"]
+        dgx = torch.zeros((rows, nd * 4 * Hp), dtype=BF16, device=self.device)
+        carry = torch.zeros((nd, B, Hp), dtype=F32, device=self.device)
+        L_.call("kbner_lstm_seq_bwd", L_.ptr(dout), dout.shape[-1], L_.ptr(saved["oc"]), L_.ptr(saved["tab"]), L_.ptr(saved["tab"]),
+                L_.ptr(whh_t), L_.ptr(saved["gates"]), L_.ptr(saved["cs"]), L_.ptr(carry), L_.ptr(dgx), dgx.shape[-1], saved["steps"], B,
+                Hp, nd, L_.stream_ptr())
+        return dgx
+
     def run_stepwise(self, gx, gxi, outi, out, out_dir_stride, B, col=0):
         """the same recurrence through the one-wave-per-tile step kernel, one library call per time step (kept as the A/B and
         cross-check of kbner_lstm_seq)"""
@@ -104,11 +139,31 @@ def step_tables(lengths, n, bidirectional=True):
     return np.stack([fwd, bwd], 1).astype(np.int32)
 
 
+def check_prefix_active(gxi, rows, ndir, B):
+    """The training contract of kbner_lstm_seq_train / kbner_lstm_seq_bwd, which the library cannot check (the tables live in
+    device memory): int [steps, ndir, B], entries -1 or a row of [0, rows), every (direction, sequence) active for steps
+    0 .. len - 1 and finished after, no (direction, row) consumed twice.  -> the table as contiguous int32."""
+    t = np.asarray(gxi)
+    if t.ndim != 3 or t.shape[1] != ndir or t.shape[2] != B or not np.issubdtype(t.dtype, np.integer):
+        raise L_.KbnerError("LSTM training row table: int [steps, %d, %d]" % (ndir, B))
+    if t.size and (t.min() < -1 or t.max() >= rows):
+        raise L_.KbnerError("LSTM training row table: entries are -1 or a row below %d" % rows)
+    act = t >= 0
+    if (act[1:] & ~act[:-1]).any():
+        raise L_.KbnerError("LSTM training row table: a sequence is active after it finished (the table must be prefix-active)")
+    for d in range(ndir):
+        r = t[:, d][act[:, d]]
+        if len(np.unique(r)) != len(r):
+            raise L_.KbnerError("LSTM training row table: a row is consumed twice by one direction")
+    return np.ascontiguousarray(t, np.int32)
+
+
 class BiLSTMHead:
     """BiLSTM(D -> hidden, 1 layer) + linear(2*hidden -> T) on the concatenated features (sequence_tagger_model.py:969-1027)."""
 
-    def __init__(self, rnn_state, linear_w, linear_b, blocks, hidden, device):
+    def __init__(self, rnn_state, linear_w, linear_b, blocks, hidden, device, transitions=None, trainable=False):
         """rnn_state: torch.nn.LSTM state dict (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0 and *_reverse);
+        trainable (off by default: nothing more is allocated): enable_training() on this state and `transitions`;
         blocks: the widths D_i of the concatenated feature blocks in the reference's order (sorted embedding names).  Inside X
         every block starts at a multiple of 32 columns (`self.cols[i]`), so a producer whose width is padded (a 1000-unit LM
         writes 1024 columns, the last 24 zero) never touches its neighbour; Wih's columns are placed to match."""
@@ -143,6 +198,10 @@ class BiLSTMHead:
         self.lin_w = wl.to(self.device).contiguous()
         self.lin_b = torch.as_tensor(linear_b, dtype=F32).to(self.device).contiguous()
         self.T = T
+        self.arena = None
+        self.training = False
+        if trainable:
+            self.enable_training(rnn_state, linear_w, linear_b, transitions)
 
     def rows(self, B, n):
         return _round_up(max(B * n, 1), 128)
@@ -162,6 +221,251 @@ class BiLSTMHead:
             self.grp.run(gx, tab, tab, out, Hp, B)
             em = ops.head_fwd(out[:B * n], self.lin_w, self.lin_b)
         return em.view(B, n, self.T)
+
+
+    # ------------------------------------------------------------------ training (opt-in)
+    # One flat fp32 arena p with a gradient buffer g and a bf16 shadow of the two GEMM / recurrence operands, in the padded device
+    # layouts.  The reference's two parameter groups (finetune_trainer.py:552-571) are two contiguous ranges:
+    #   [ Wih [8Hp, Dq] | Whh [2, 4Hp, Hp] | bias_ih [8Hp] | bias_hh [8Hp] | transitions [T, T] ]  at lr * lr_rate   (shadow: Wih, Whh)
+    #   [ linear.weight [T, 2Hp] | linear.bias [T] ]                                                at lr
+    # Dq = Dp rounded up to 128: the weight-gradient GEMM dWih = dgx^T X takes N in multiples of 128, so the TRAINING side pads X and
+    # Wih (zero columns); the inference layout (Dp, new_input) is as it was.  dWhh comes from one GEMM against the two-direction-wide
+    # hprev [rows, 2Hp] whose cross blocks are discarded.  bias_ih and bias_hh stay two parameters (the reference trains both; they
+    # receive the same gradient, so under AdamW their sum moves twice); the forward adds them.  Padded entries have zero weights and
+    # receive exactly zero gradients (a padded unit's gates see dh = 0 and carry 0), so they stay zero.
+    _FIELDS = ("wih", "whh", "bias_ih", "bias_hh", "transitions", "linear.weight", "linear.bias")
+
+    def enable_training(self, rnn_state, linear_w, linear_b, transitions):
+        Hp, T = self.Hp, self.T
+        self.Dq = _round_up(self.Dp, 128)
+        shapes = {"wih": (8 * Hp, self.Dq), "whh": (2, 4 * Hp, Hp), "bias_ih": (8 * Hp,), "bias_hh": (8 * Hp,), "transitions": (T, T),
+                  "linear.weight": (T, 2 * Hp), "linear.bias": (T,)}
+        self.shapes, self.offsets, off = shapes, {}, 0
+        for k in self._FIELDS:
+            self.offsets[k] = off
+            off += _round_up(int(np.prod(shapes[k])), 4)
+        self.n = off
+        self.n_shadow = self.offsets["bias_ih"]
+        self.split = self.offsets["linear.weight"]
+        dev = self.device
+        self.arena = torch.zeros(self.n, dtype=F32, device=dev)
+        self.g = torch.zeros(self.n, dtype=F32, device=dev)
+        self.shadow = torch.zeros(self.n_shadow, dtype=BF16, device=dev)
+        self.dropout = self.word_dropout = self.locked_dropout = 0.0
+        self._drop_rng = np.random.default_rng(0)
+        self.last_drop = None
+        self.load_state({"rnn": rnn_state, "linear.weight": linear_w, "linear.bias": linear_b, "transitions": transitions})
+
+    def param(self, name, buf=None):
+        buf = self.arena if buf is None else buf
+        o, shp = self.offsets[name], self.shapes[name]
+        return buf[o:o + int(np.prod(shp))].view(shp)
+
+    def grad(self, name):
+        return self.param(name, self.g)
+
+    def load_state(self, state):
+        """the reference-layout dict load_stack_state takes -> the arena (padded layouts); the inverse of state()"""
+        Hp, H, T = self.Hp, self.H, self.T
+        rnn = state["rnn"]
+        self.arena.zero_()
+        wih, whh = torch.zeros(self.shapes["wih"], dtype=F32), torch.zeros(self.shapes["whh"], dtype=F32)
+        bih, bhh = torch.zeros(8 * Hp, dtype=F32), torch.zeros(8 * Hp, dtype=F32)
+        for d, sfx in enumerate(("", "_reverse")):
+            w = self.grp.pad_gates(rnn["weight_ih_l0" + sfx])
+            ref = 0
+            for width, xc in zip(self.blocks, self.cols):
+                wih[d * 4 * Hp:(d + 1) * 4 * Hp, xc:xc + width] = w[:, ref:ref + width]
+                ref += width
+            whh[d, :, :H] = self.grp.pad_gates(rnn["weight_hh_l0" + sfx])
+            bih[d * 4 * Hp:(d + 1) * 4 * Hp] = self.grp.pad_gates(rnn["bias_ih_l0" + sfx])
+            bhh[d * 4 * Hp:(d + 1) * 4 * Hp] = self.grp.pad_gates(rnn["bias_hh_l0" + sfx])
+        lw = torch.as_tensor(state["linear.weight"], dtype=F32)
+        wl = torch.zeros((T, 2 * Hp), dtype=F32)
+        wl[:, :H], wl[:, Hp:Hp + H] = lw[:, :H], lw[:, H:2 * H]
+        for k, v in (("wih", wih), ("whh", whh), ("bias_ih", bih), ("bias_hh", bhh), ("linear.weight", wl),
+                     ("linear.bias", torch.as_tensor(state["linear.bias"], dtype=F32)),
+                     ("transitions", torch.as_tensor(state["transitions"], dtype=F32))):
+            self.param(k).copy_(v.to(self.device))
+        self.shadow.copy_(self.arena[:self.n_shadow])
+        self.g.zero_()
+        self._refresh()
+
+    def state(self, buf=None):
+        """the arena (or a buffer laid out like it) in the reference's layout: {"rnn": torch.nn.LSTM state dict, "linear.weight",
+        "linear.bias", "transitions"} (host float32).  load_state(state()) reproduces the arena bit for bit."""
+        Hp, H = self.Hp, self.H
+        unpad = lambda t: torch.cat([t[q * Hp:q * Hp + H] for q in range(4)], 0)   # noqa: E731
+        p = {k: self.param(k, buf).detach().cpu() for k in self._FIELDS}
+        rnn = {}
+        for d, sfx in enumerate(("", "_reverse")):
+            w = unpad(p["wih"][d * 4 * Hp:(d + 1) * 4 * Hp])
+            rnn["weight_ih_l0" + sfx] = torch.cat([w[:, xc:xc + width] for width, xc in zip(self.blocks, self.cols)], 1).contiguous()
+            rnn["weight_hh_l0" + sfx] = unpad(p["whh"][d])[:, :H].contiguous()
+            rnn["bias_ih_l0" + sfx] = unpad(p["bias_ih"][d * 4 * Hp:(d + 1) * 4 * Hp]).contiguous()
+            rnn["bias_hh_l0" + sfx] = unpad(p["bias_hh"][d * 4 * Hp:(d + 1) * 4 * Hp]).contiguous()
+        lw = p["linear.weight"]
+        return {"rnn": rnn, "linear.weight": torch.cat([lw[:, :H], lw[:, Hp:Hp + H]], 1).contiguous(),
+                "linear.bias": p["linear.bias"].clone(), "transitions": p["transitions"].clone()}
+
+    def state_of(self, buf):
+        """a buffer laid out like the arena (the gradient, an optimizer moment) in the reference's layout"""
+        return self.state(buf)
+
+    def _refresh(self):
+        """after the arena changed (optimizer step, load_state): what emissions() and loss_backward() read"""
+        Hp = self.Hp
+        sh = self.shadow
+        self.wih_t = sh[:8 * Hp * self.Dq].view(8 * Hp, self.Dq)
+        self.wih = self.wih_t if self.Dq == self.Dp else self.wih_t[:, :self.Dp].contiguous()
+        self.grp.whh = sh[self.offsets["whh"]:self.n_shadow].view(2, 4 * Hp, Hp)
+        self.bias = self.param("bias_ih") + self.param("bias_hh")
+        self.lin_w, self.lin_b = self.param("linear.weight"), self.param("linear.bias")
+        self._whht = None
+
+    def seed_dropout(self, seed):
+        self._drop_rng = np.random.default_rng(int(seed))
+
+    def train(self, mode=True):
+        self.training = bool(mode) and self.arena is not None
+        return self
+
+    def _draw_dropout(self, n):
+        """one training forward's dropout sites, drawn from the head's counter-based stream: (word-dropped positions bool [n] or
+        None, pre-RNN (element, locked) sites, post-RNN (element, locked) sites), each site a (seed, thresh) pair"""
+        if not self.training or not (self.dropout or self.word_dropout or self.locked_dropout):
+            return None
+        word = (self._drop_rng.random(n) < self.word_dropout) if self.word_dropout > 0.0 else None
+        sd = self._drop_rng.integers(0, 2 ** 32, size=4, dtype="uint64")
+        te, tl = ops.drop_thresh(self.dropout), ops.drop_thresh(self.locked_dropout)
+        return word, ((int(sd[0]), te), (int(sd[1]), tl)), ((int(sd[2]), te), (int(sd[3]), tl))
+
+    def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw"):
+        """One micro-batch of head training on constant features: forward, CRF NLL, and loss_scale * its gradient ADDED to self.g.
+        X bf16 [rows, Dp] as new_input() lays it out; batch: the device dict of kbner.batch (ctags i32 [B, nc], clens i32 [B],
+        cfeat_idx i32 [B * nc]: the S-X compaction of the emissions); weights f32 [B] replace the 1 / B of the batch mean.
+        Sequence (sequence_tagger_model.py:959-964,969-994,1027 and the CRF loss): the three pre-RNN dropouts as one
+        gather_rows_drop over X with an identity index (WordDropout: index -1), input GEMM, kbner_lstm_seq_train, the two post-RNN
+        dropouts, head, compaction, CRF NLL forward / backward, and back through the same chain to kbner_lstm_seq_bwd and the weight
+        gradients.  Nothing flows into X.  -> the loss, a 0-d device tensor."""
+        if self.arena is None:
+            raise L_.KbnerError("this BiLSTMHead was not built for training (enable_training())")
+        with L_.stream_scope():
+            dev, Hp, T, R = self.device, self.Hp, self.T, B * n
+            Mp = X.shape[0]
+            sites = self._draw_dropout(n) if drop == "draw" else drop
+            self.last_drop = sites
+            ident = None
+            if sites is not None:
+                word, pre, post = sites
+                ident = torch.arange(R, dtype=I32, device=dev)
+                idx = ident
+                if word is not None:
+                    idx = torch.where(torch.from_numpy(np.tile(word, B)).to(dev), torch.full_like(ident, -1), ident)
+                Xd = torch.zeros((Mp, self.Dp), dtype=BF16, device=dev)
+                ops.gather_rows_drop(X, idx, n, pre[0], pre[1], out=Xd)
+                X = Xd
+            if self.Dq != self.Dp:
+                Xt = torch.zeros((Mp, self.Dq), dtype=BF16, device=dev)
+                Xt[:, :self.Dp] = X
+            else:
+                Xt = X
+            gx = torch.empty((Mp, 8 * Hp), dtype=BF16, device=dev)
+            ops.gemm(GEMM_NT, Xt, self.wih_t, Mp, 8 * Hp, self.Dq, C=gx, bias=self.bias, epi=EPI_BIAS)
+            out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
+            saved = self.grp.run_train(gx, step_tables(lengths, n), out, B, [0, Hp])
+            post_on = sites is not None and bool(post[0][1] or post[1][1])
+            feat = ops.gather_rows_drop(out, ident, n, post[0], post[1]) if post_on else out[:R]
+            em = ops.head_fwd(feat, self.lin_w, self.lin_b)
+            self.last_out, self.last_feat = out, feat      # (tests read the dropout sites back from these)
+            nc = batch["ctags"].shape[1]
+            comp = ops.gather_rows_f32(em, batch["cfeat_idx"]).view(B, nc, T)
+            trans = self.param("transitions")
+            logz, gold, alpha = ops.crf_nll_fwd(comp, trans, batch["ctags"], batch["clens"], start, stop)
+            w = torch.full((B,), 1.0 / B, dtype=F32, device=dev) if weights is None else torch.as_tensor(
+                weights, dtype=F32, device=dev).contiguous()
+            if w.numel() != B:
+                raise ValueError("weights must hold one value per sentence")
+            loss = torch.empty((1,), dtype=F32, device=dev)
+            ops.wdiff_sum(logz, gold, w, loss)
+            self.last_emissions = em.view(B, n, T)
+            # ---- backward
+            dcomp = ops.crf_nll_bwd(comp, trans, batch["ctags"], batch["clens"], alpha, logz, w * float(loss_scale), start, stop,
+                                    self.grad("transitions"))
+            dem = torch.zeros((R, T), dtype=F32, device=dev)
+            # (kbner_scatter_rows_f32 moves float4s: tag counts that are no multiple of 4 take the adding scatter onto the zeros)
+            (ops.scatter_rows_f32 if T % 4 == 0 else ops.scatter_add_rows_f32)(dcomp.view(B * nc, T), batch["cfeat_idx"], dem)
+            dfeat = ops.head_bwd(dem, feat, self.lin_w, self.grad("linear.weight"), self.grad("linear.bias"))
+            if post_on:
+                dout = torch.zeros((R, 2 * Hp), dtype=BF16, device=dev)
+                ops.scatter_rows_drop(dfeat, ident, dout, n, post[0], post[1])
+            else:
+                dout = dfeat
+            if self._whht is None:
+                self._whht = self.grp.whh_t()
+            dgx = self.grp.run_bwd(dout, saved, self._whht)
+            # weight gradients: fp32 atomic accumulation on the 128x128 kernel (lda given: it takes N in multiples of 128), the row
+            # (reduction) dimension split until the launch has enough workgroups
+            sk = 1
+            while (8 * Hp // 128) * (self.Dq // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
+                sk *= 2
+            ops.gemm(GEMM_TN, dgx, Xt, 8 * Hp, self.Dq, Mp, C32=self.grad("wih"), epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
+            cross = torch.zeros((8 * Hp, 2 * Hp), dtype=F32, device=dev)
+            sk = 1
+            while (8 * Hp // 128) * (2 * Hp // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
+                sk *= 2
+            ops.gemm(GEMM_TN, dgx, saved["hprev"], 8 * Hp, 2 * Hp, Mp, C32=cross, epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
+            gw = self.grad("whh")
+            gw[0] += cross[:4 * Hp, :Hp]
+            gw[1] += cross[4 * Hp:, Hp:]
+            ops.colsum(dgx, self.grad("bias_ih"))
+            ops.colsum(dgx, self.grad("bias_hh"))
+        return loss[0]
+
+
+class StackOptimizer:
+    """The optimizer of a trainable BiLSTMHead over its arena ranges: `linear.*` at lr, `rnn.*` and `transitions` at lr * lr_rate
+    (the reference's two parameter groups, finetune_trainer.py:552-571), clip_grad_norm_(max_norm) from kbner_grad_sqnorm, then
+    kbner_adamw_hf (HF AdamW: eps 1e-6, weight decay 0, bias correction) or kbner_sgd.  lr_scale multiplies both rates (the
+    trainer's schedule)."""
+
+    def __init__(self, head, name="AdamW", lr=5e-3, lr_rate=1.0, betas=(0.9, 0.999), eps=1e-6, max_norm=5.0):
+        if name not in ("AdamW", "SGD"):
+            raise NotImplementedError("optimizer %r: the stacked tagger trains with AdamW or SGD" % (name,))
+        if head.arena is None:
+            raise L_.KbnerError("StackOptimizer needs a trainable BiLSTMHead (enable_training())")
+        self.head, self.name, self.lr, self.lr_rate, self.betas, self.eps, self.max_norm = head, name, lr, lr_rate, betas, eps, max_norm
+        self.t = 0
+        self.lr_scale = 1.0
+        self.ws = torch.zeros(L_.load().kbner_sqnorm_ws_floats(), dtype=F32, device=head.device)
+        self.norm_sq = torch.zeros(1, dtype=F32, device=head.device)
+        self.reset()
+
+    def reset(self):
+        """drop the moments (a new state was loaded into the head)"""
+        h = self.head
+        self.m = torch.zeros(h.n, dtype=F32, device=h.device) if self.name == "AdamW" else None
+        self.v = torch.zeros(h.n, dtype=F32, device=h.device) if self.name == "AdamW" else None
+        self.t = 0
+
+    def step(self, grad_scale=1.0):
+        """clip, update, zero the gradient, refresh the head's shadow views -> the squared gradient norm (device, before scaling)"""
+        h = self.head
+        with L_.stream_scope():
+            ops.grad_sqnorm(h.g, self.ws, self.norm_sq)
+            self.t += 1
+            b1, b2 = self.betas
+            bc = (1.0 - b2 ** self.t) ** 0.5 / (1.0 - b1 ** self.t)
+            for lo, hi, lr in ((0, h.split, self.lr * self.lr_rate * self.lr_scale), (h.split, h.n, self.lr * self.lr_scale)):
+                nsh = h.n_shadow if lo == 0 else 0
+                sh = h.shadow if nsh else None
+                if self.name == "AdamW":
+                    ops.adamw(h.arena[lo:hi], h.g[lo:hi], self.m[lo:hi], self.v[lo:hi], sh, nsh, lr * bc, 0.0, b1, b2, self.eps,
+                              self.norm_sq, self.max_norm, grad_scale, True)
+                else:
+                    ops.sgd(h.arena[lo:hi], h.g[lo:hi], sh, nsh, lr, self.norm_sq, self.max_norm, grad_scale, True)
+            h._refresh()
+        return self.norm_sq
 
 
 class CharLM:

@@ -141,6 +141,13 @@ def main():
 
 def _load_trained(student, base_path):
     import torch
+    if getattr(student, "use_rnn", False):
+        # a stacked tagger trained by ModelFinetuner: the head's weights in the reference's layout (load_stack_state)
+        f = Path(base_path) / "stack-model.pt"
+        if not f.exists():
+            raise FileNotFoundError("no stack-model.pt under %s" % base_path)
+        student.load_stack_state(torch.load(str(f), map_location="cpu", weights_only=False))
+        return
     for name in ("best-model.pt", "final-model.pt"):
         f = Path(base_path) / name
         if f.exists():
