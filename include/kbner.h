@@ -178,6 +178,20 @@ int kbner_gather_rows_drop(const kbner_bf16* src, const int* idx, kbner_bf16* ou
                            uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 int kbner_scatter_rows_drop(const kbner_bf16* dout, const int* idx, kbner_bf16* dsrc, int R, int H, int n, uint32_t seed_e,
                             uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+/* The stacked tagger's padded input matrix assembled from STORED feature rows: the concatenation with the embedding selection
+ * (sequence_tagger_model.py:879-891: cat of features * selection[idx]) and the pre-RNN dropouts (:959-964) in one pass over compact
+ * rows that were computed once (flair's embeddings_storage_mode; kbner.stack.FeatureStore).  store bf16 [*, ld_store]; idx i32 [R]
+ * (-1 = zero row: padding positions, WordDropout; may repeat); block_col i32 [nblk + 1], ascending multiples of 8; block_on u8 [nblk];
+ * all three tables in DEVICE memory.  For r < R_out, c < ld_out:
+ *   out[r, c] = (r < R && c < W && idx[r] >= 0 && block_on[blk(c)]) ? bf16(store[idx[r], c] * (m_e(r, c) * m_l(r / n, c))) : 0
+ * blk(c): the block with block_col[b] <= c < block_col[b + 1]; columns outside every block are 0.  m_e, m_l: the two sites of
+ * kbner_gather_rows_drop (same keys, product in fp32, one rounding; a threshold of 0 disables its site).  EVERY element of
+ * out[0:R_out, 0:ld_out] is written -- columns W .. ld_out - 1 and rows R .. R_out - 1 are the training layout's zero padding -- so the
+ * caller zero-fills nothing.  1 <= nblk <= 64; W, ld_store, ld_out multiples of 8; block_col[nblk] <= W <= ld_store; W <= ld_out;
+ * n >= 1, R % n == 0, R <= R_out.  (The table conditions live in device memory: kbner.ops checks them on the host copy.) */
+int kbner_gather_rows_blocks_drop(const kbner_bf16* store, int ld_store, const int* idx, const int* block_col,
+                                  const unsigned char* block_on, int nblk, kbner_bf16* out, int ld_out, int R, int R_out, int W, int n,
+                                  uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
 /* Encoder layer selection of TransformerWordEmbeddings (layers="-1,-2,-3,-4" / 'all', use_scalar_mix): the gather of the first
  * sub-token rows over k hidden states at once, replacing the per-layer selection, torch.cat and torch.mean of
  * flair/embeddings.py:2983-2991, 3315-3343 (the reference's use_scalar_mix IS torch.mean over the selected rows, :3337; its

@@ -231,6 +231,61 @@ __global__ __launch_bounds__(256) void gather_rows_ld_kernel(const bf16_t* __res
   *reinterpret_cast<uint4*>(out + (size_t)r * ld_out + c * 8) = v;
 }
 
+// The stacked tagger's padded input matrix assembled from STORED feature rows (kbner/stack.py FeatureStore: compact bf16 rows
+// [tokens, ld_store], computed once while the embeddings are frozen), with the embedding selection (sequence_tagger_model.py:879-891:
+// features * selection[idx]) and the head's pre-RNN dropouts (:959-964, the two sites of rows_drop_kernel, same keys) applied on the
+// way through:
+//     out[r, c] = (r < R && c < W && idx[r] >= 0 && block_on[blk(c)]) ? bf16(store[idx[r], c] * m[r, c]) : 0      r < R_out, c < ld_out
+// blk(c): the block with block_col[b] <= c < block_col[b + 1] (boundaries are multiples of 8, so a 16-byte chunk lies in one block;
+// columns outside every block are zero).  The kernel writes EVERY element of out[0:R_out, 0:ld_out] -- the rows behind R and the
+// columns behind W are the training layout's padding -- so nothing is zero-filled beforehand.  Same shape as rows_drop_kernel: one
+// wave per row, the 512-column chunk of the output row as the outer loop, so the chunk's block switch and column keys stay in
+// registers over the rows.  DROP = false (both sites off): a copy.
+template <bool DROP>
+__global__ __launch_bounds__(256) void gather_rows_blocks_kernel(const bf16_t* __restrict__ store, int ld_store,
+                                                                 const int* __restrict__ idx, const int* __restrict__ block_col,
+                                                                 const unsigned char* __restrict__ block_on, int nblk,
+                                                                 bf16_t* __restrict__ out, int ld_out, int R, int R_out, int W, int n,
+                                                                 uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l,
+                                                                 uint32_t thresh_l) {
+  const int lane = threadIdx.x % 64;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + threadIdx.x / 64);
+  const int nwave = gridDim.x * 4;
+  const float scale = drop_scale(thresh_e) * drop_scale(thresh_l);
+  for (int c0 = lane * 8; c0 < ld_out; c0 += 512) {
+    bool on = false;
+    if (c0 < W)
+      for (int b = 0; b < nblk; ++b)
+        if (block_col[b] <= c0 && c0 < block_col[b + 1]) on = block_on[b] != 0;
+    uint32_t cke[8], ckl[8];
+    if (DROP) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        cke[j] = drop_colkey(seed_e, (uint32_t)(c0 + j));
+        ckl[j] = drop_colkey(seed_l, (uint32_t)(c0 + j));
+      }
+    }
+    for (int r = wave; r < R_out; r += nwave) {
+      const int s = r < R ? idx[r] : -1;
+      uint4 u = make_uint4(0, 0, 0, 0);
+      if (on && s >= 0) {
+        u = *reinterpret_cast<const uint4*>(store + (size_t)s * ld_store + c0);
+        if (DROP) {
+          const uint32_t rke = drop_rowkey(seed_e, (uint32_t)r);
+          const uint32_t rkl = drop_rowkey(seed_l, (uint32_t)(r / n));
+          float v[8];
+          unpack8bf(u, v);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[j] *= (drop_keep(rke, cke[j], thresh_e) && drop_keep(rkl, ckl[j], thresh_l)) ? scale : 0.0f;
+          u = pack8bf(v);
+        }
+      }
+      *reinterpret_cast<uint4*>(out + (size_t)r * ld_out + c0) = u;
+    }
+  }
+}
+
 // fp32 row scatter (data-parallel exchange of the touched word-embedding gradient rows, kbner/dp.py): dst[idx[r],:] = rows[r,:];
 // indices unique, 16-byte accesses (W % 4 == 0)
 __global__ __launch_bounds__(256) void scatter_rows_f32_kernel(const float4* __restrict__ rows, const int* __restrict__ idx,
@@ -345,6 +400,24 @@ int kbner_gather_rows_ld(const bf16_t* src, int ld_src, const int* idx, bf16_t* 
   KBNER_CHECK_ARG(R >= 0 && H > 0 && H % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0);
   if (R == 0) return 0;
   FLAT_LAUNCH(gather_rows_ld_kernel, (size_t)R * (H / 8), stream, src, ld_src, idx, out, ld_out, R, H / 8);
+  KBNER_LAUNCH_RET();
+}
+
+// idx, block_col, block_on: DEVICE memory.  What the tables must hold (block_col ascending multiples of 8, block_col[nblk] <= W) cannot
+// be checked here; kbner.ops checks the host copy.  Whatever they hold, no access leaves store[idx[r], 0:W] or out[0:R_out, 0:ld_out].
+int kbner_gather_rows_blocks_drop(const bf16_t* store, int ld_store, const int* idx, const int* block_col, const unsigned char* block_on,
+                                  int nblk, bf16_t* out, int ld_out, int R, int R_out, int W, int n, uint32_t seed_e, uint32_t thresh_e,
+                                  uint32_t seed_l, uint32_t thresh_l, void* stream) {
+  KBNER_CHECK_ARG(nblk >= 1 && nblk <= 64 && R >= 0 && R <= R_out && n >= 1 && R % n == 0);
+  KBNER_CHECK_ARG(W > 0 && W % 8 == 0 && ld_store % 8 == 0 && ld_out % 8 == 0 && W <= ld_store && W <= ld_out);
+  if (R_out == 0) return 0;
+  KBNER_CHECK_ARG(out != nullptr && block_col != nullptr && block_on != nullptr && (R == 0 || (store != nullptr && idx != nullptr)));
+  if (thresh_e == 0 && thresh_l == 0)
+    hipLaunchKernelGGL(gather_rows_blocks_kernel<false>, dim3(rows_grid(R_out)), dim3(256), 0, (hipStream_t)stream, store, ld_store, idx,
+                       block_col, block_on, nblk, out, ld_out, R, R_out, W, n, seed_e, thresh_e, seed_l, thresh_l);
+  else
+    hipLaunchKernelGGL(gather_rows_blocks_kernel<true>, dim3(rows_grid(R_out)), dim3(256), 0, (hipStream_t)stream, store, ld_store, idx,
+                       block_col, block_on, nblk, out, ld_out, R, R_out, W, n, seed_e, thresh_e, seed_l, thresh_l);
   KBNER_LAUNCH_RET();
 }
 

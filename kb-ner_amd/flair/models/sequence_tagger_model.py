@@ -366,9 +366,55 @@ class SequenceTagger(flair.nn.Model):
         self.mask = (torch.arange(n, device=feats.device)[None, :] < torch.from_numpy(lengths).to(feats.device)[:, None]).float()
         return feats
 
+    # The feature store (flair's embeddings_storage_mode for the frozen stack: kbner.stack.FeatureStore).  Closed by default: with no
+    # store open every call below launches what it launched before the store existed.
+    def open_feature_store(self, mode):
+        """mode "gpu" / "cpu": keep every sentence's frozen features after their first computation (device memory / pinned host
+        memory); "none": no store.  -> the store (None for "none")"""
+        from kbner.stack import FeatureStore
+        if not self.use_rnn:
+            raise ValueError("open_feature_store() belongs to the stacked tagger (use_rnn: true): the fine-tuning path's features "
+                             "change with every step")
+        self.close_feature_store()
+        if mode in (None, "none"):
+            return None
+        head = self.stack_head
+        self._feature_store = FeatureStore(mode, head.Dp, list(head.cols) + [head.Dp], flair.device)
+        return self._feature_store
+
+    def close_feature_store(self):
+        store = self.__dict__.get("_feature_store")
+        if store is not None:
+            store.close()
+        self._feature_store = None
+
+    def _stack_selection(self):
+        return self.selection if (getattr(self, "embedding_selector", False) and self.selection is not None) else None
+
+    def _stack_source(self, sentences, n):
+        """the batch's rows in the open feature store (FeatureStore.source) -- None: no store, or a sentence is missing"""
+        store = self.__dict__.get("_feature_store")
+        if store is None:
+            return None
+        sel = self._stack_selection()
+        store.select([True] * store.nblk if sel is None else [float(sel[slot]) != 0.0 for slot in range(store.nblk)])
+        return store.source(sentences, n)
+
     def _stack_input(self, sentences):
         """the concatenated feature matrix X bf16 [rows, Dp] (token-major rows b*n + t; block `slot` at columns
-        stack_head.cols[slot]), filled in place by the selected embeddings' device producers -> (X, lengths, B, n)"""
+        stack_head.cols[slot]; zero rows at padding) -> (X, lengths, B, n).  With a feature store open and every sentence in it: one
+        kbner_gather_rows_blocks_drop from the stored rows; otherwise computed by the producers (and stored)."""
+        from kbner.stack import FeatureStore
+        lengths = np.asarray([len(s) for s in sentences], np.int64)
+        B, n = len(sentences), int(lengths.max())
+        src = self._stack_source(sentences, n)
+        if src is None:
+            return self._stack_compute(sentences)
+        head = self.stack_head
+        return FeatureStore.launch(src, head.rows(B, n), head.Dp), lengths, B, n
+
+    def _stack_compute(self, sentences):
+        """X filled in place by the selected embeddings' device producers; added to an open feature store"""
         from kbner import batch as kb
         from kbner import ops
         from flair.embeddings import BertEmbeddings, FlairEmbeddings, TransformerWordEmbeddings
@@ -377,7 +423,7 @@ class SequenceTagger(flair.nn.Model):
         n = int(lengths.max())
         head = self.stack_head
         X = head.new_input(B, n)
-        sel = self.selection if (getattr(self, "embedding_selector", False) and self.selection is not None) else None
+        sel = self._stack_selection()
         char_lms = []
         for slot, emb in enumerate(self._stack_embs):
             if sel is not None and float(sel[slot]) == 0.0:
@@ -418,6 +464,9 @@ class SequenceTagger(flair.nn.Model):
                     cache[key] = CharLMGroup([e.engine(flair.device) for e, _ in members])
                 batches = [e.char_batch(sentences, n) for e, _ in members]
                 cache[key].run([b[0] for b in batches], [b[1] for b in batches], X, [c for _, c in members])
+        store = self.__dict__.get("_feature_store")
+        if store is not None:
+            store.add(sentences, X, lengths, n)
         return X, lengths, B, n
 
     def train(self, mode: bool = True):
@@ -597,7 +646,10 @@ class SequenceTagger(flair.nn.Model):
         if isinstance(data_points, Sentence):
             data_points = [data_points]
         head = self.enable_stack_training()
-        X, lengths, B, n = self._stack_input(data_points)
+        lengths = np.asarray([len(s) for s in data_points], np.int64)
+        B, n = len(data_points), int(lengths.max())
+        src = self._stack_source(data_points, n)     # a store hit: the head reads the stored rows itself, X is never assembled
+        X = None if src is not None else self._stack_compute(data_points)[0]
         tags = np.zeros((B, n), np.int64)
         for b, s in enumerate(data_points):
             t = getattr(s, self.tag_type + "_tags", None)
@@ -610,7 +662,8 @@ class SequenceTagger(flair.nn.Model):
         db = kb.to_device(hb, flair.device)
         self._last = (hb, db)
         self.mask = db["keep_f"]
-        loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale, weights=sentence_weights)
+        loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale, weights=sentence_weights,
+                                  source=src)
         self.last_loss_parts = (loss, None)
         return loss
 

@@ -642,64 +642,76 @@ class ModelFinetuner:
         best_score, bad_epochs = -1.0, 0
         dev_score_history, dev_loss_history, train_loss_history = [], [], []
         hook = getattr(self, "stack_step_hook", None)     # tests: called after every optimizer step with (its batches, their losses)
+        # embeddings_storage_mode (the reference keeps the frozen embeddings on the sentences after their first computation): "gpu" /
+        # "cpu" open the tagger's feature store, which training, the dev evaluations and final_test below read; "none": no store
+        storage = str(a["embeddings_storage_mode"]).lower()
+        if storage not in ("none", "cpu", "gpu"):
+            raise ValueError("embeddings_storage_mode must be 'none', 'cpu' or 'gpu' (got %r)" % (a["embeddings_storage_mode"],))
+        store = model.open_feature_store(storage)
         try:
-            for epoch in range(self.epoch, int(a["max_epochs"])):
-                if a["shuffle"]:
-                    rng.shuffle(order)
-                model.train()
-                tot, cnt, t_ep, seen = 0.0, 0, time.time(), 0
-                for g0 in range(0, len(order), accum):
-                    group = order[g0:g0 + accum]
-                    losses = []
-                    for bi in group:
-                        batch = loader[bi]
-                        losses.append(model.forward_backward(batch, loss_scale=1.0 / len(group)))
-                        seen += len(batch)
-                        store_embeddings(batch, "none")
-                    opt.lr_scale = linear_scale(opt.t) if linear else plateau
-                    opt.step()
-                    if hook is not None:
-                        hook([loader[bi] for bi in group], losses)
-                    tot += float(sum(losses)) / len(group)
-                    cnt += 1
-                train_loss = tot / max(cnt, 1)
-                train_loss_history.append(train_loss)
-                model.trained_epochs = epoch + 1
-                model.eval()
-                lr_now = lr0 * (linear_scale(opt.t) if linear else plateau)
+            try:
+                for epoch in range(self.epoch, int(a["max_epochs"])):
+                    if a["shuffle"]:
+                        rng.shuffle(order)
+                    model.train()
+                    tot, cnt, t_ep, seen = 0.0, 0, time.time(), 0
+                    for g0 in range(0, len(order), accum):
+                        group = order[g0:g0 + accum]
+                        losses = []
+                        for bi in group:
+                            batch = loader[bi]
+                            losses.append(model.forward_backward(batch, loss_scale=1.0 / len(group)))
+                            seen += len(batch)
+                            store_embeddings(batch, "none")
+                        opt.lr_scale = linear_scale(opt.t) if linear else plateau
+                        opt.step()
+                        if hook is not None:
+                            hook([loader[bi] for bi in group], losses)
+                        tot += float(sum(losses)) / len(group)
+                        cnt += 1
+                    train_loss = tot / max(cnt, 1)
+                    train_loss_history.append(train_loss)
+                    model.trained_epochs = epoch + 1
+                    model.eval()
+                    lr_now = lr0 * (linear_scale(opt.t) if linear else plateau)
+                    log_line(log)
+                    log.info("EPOCH %d done: loss %.4f - lr %.2e - %.1f sentences/sec", epoch + 1, train_loss, lr_now, seen / max(time.time() - t_ep, 1e-9))
+                    f1s, dls = [], []
+                    for dname, dl in zip(getattr(self.corpus, "targets", ["dev"]), dev_loaders):
+                        res, dl_loss = model.evaluate(dl, embeddings_storage_mode="none")
+                        log.info("%s DEV : loss %.4f - f1 %.4f - macro %.4f", dname, dl_loss, res.main_score, res.macro_score)
+                        f1s.append((res.macro_score if a["select_model_by_macro"] else res.main_score) * 100)
+                        dls.append(dl_loss)
+                    score = sum(f1s) / len(f1s)
+                    dev_score_history.append(score)
+                    dev_loss_history.append(sum(dls) / len(dls))
+                    if store is not None:
+                        log.info("feature store (%s): %d batches served, %d recomputed - %d sentences, %d rows, %d bytes", storage,
+                                 store.hits, store.misses, len(store), store.rows, store.nbytes)
+                    with open(loss_txt, "a") as f:
+                        f.write("%d\t%s\t%.3e\t%.6f\t%s\t%s\t_\n" % (epoch + 1, time.strftime("%H:%M:%S"), lr_now, train_loss, dev_loss_history[-1], score))
+                    if score > best_score:
+                        best_score, bad_epochs = score, 0
+                    else:
+                        bad_epochs += 1
+                    if score == best_score:
+                        log.info("==================Saving the current best model: %s==================", score)
+                        torch.save(model._stack_state, str(base_path / "stack-model.pt"))
+                    if not linear and bad_epochs > int(a["patience"]):
+                        plateau *= float(a["anneal_factor"])
+                        bad_epochs = 0
+                        log.info("no better dev score for %d epochs: learning rate -> %.3e", int(a["patience"]) + 1, lr0 * plateau)
+                        if lr0 * plateau < float(a["min_learning_rate"]):
+                            log.info("learning rate below min_learning_rate: stopping")
+                            break
+            except KeyboardInterrupt:
                 log_line(log)
-                log.info("EPOCH %d done: loss %.4f - lr %.2e - %.1f sentences/sec", epoch + 1, train_loss, lr_now, seen / max(time.time() - t_ep, 1e-9))
-                f1s, dls = [], []
-                for dname, dl in zip(getattr(self.corpus, "targets", ["dev"]), dev_loaders):
-                    res, dl_loss = model.evaluate(dl, embeddings_storage_mode="none")
-                    log.info("%s DEV : loss %.4f - f1 %.4f - macro %.4f", dname, dl_loss, res.main_score, res.macro_score)
-                    f1s.append((res.macro_score if a["select_model_by_macro"] else res.main_score) * 100)
-                    dls.append(dl_loss)
-                score = sum(f1s) / len(f1s)
-                dev_score_history.append(score)
-                dev_loss_history.append(sum(dls) / len(dls))
-                with open(loss_txt, "a") as f:
-                    f.write("%d\t%s\t%.3e\t%.6f\t%s\t%s\t_\n" % (epoch + 1, time.strftime("%H:%M:%S"), lr_now, train_loss, dev_loss_history[-1], score))
-                if score > best_score:
-                    best_score, bad_epochs = score, 0
-                else:
-                    bad_epochs += 1
-                if score == best_score:
-                    log.info("==================Saving the current best model: %s==================", score)
-                    torch.save(model._stack_state, str(base_path / "stack-model.pt"))
-                if not linear and bad_epochs > int(a["patience"]):
-                    plateau *= float(a["anneal_factor"])
-                    bad_epochs = 0
-                    log.info("no better dev score for %d epochs: learning rate -> %.3e", int(a["patience"]) + 1, lr0 * plateau)
-                    if lr0 * plateau < float(a["min_learning_rate"]):
-                        log.info("learning rate below min_learning_rate: stopping")
-                        break
-        except KeyboardInterrupt:
-            log_line(log)
-            log.info("Exiting from training early.")
-        final_score = 0.0
-        if self.corpus.test is not None and len(self.corpus.test) > 0:
-            final_score = self.final_test(base_path, eval_bs, quiet_mode=False)
+                log.info("Exiting from training early.")
+            final_score = 0.0
+            if self.corpus.test is not None and len(self.corpus.test) > 0:
+                final_score = self.final_test(base_path, eval_bs, quiet_mode=False)
+        finally:
+            model.close_feature_store()
         log.removeHandler(handler)
         return {"test_score": final_score, "dev_score_history": dev_score_history, "train_loss_history": train_loss_history,
                 "dev_loss_history": dev_loss_history}

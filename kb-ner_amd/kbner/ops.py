@@ -317,6 +317,48 @@ def scatter_rows_drop(dout, idx, dsrc, n, drop_e=NO_DROP, drop_l=NO_DROP):
     L.call("kbner_scatter_rows_drop", ptr(dout), ptr(idx), ptr(dsrc), R, H, n, se, te, sl, tl, stream_ptr())
 
 
+def check_block_cols(block_col, W):
+    """The table contract of kbner_gather_rows_blocks_drop, which the library cannot check (the table lives in device memory): 2 to 65
+    ascending column boundaries, each a multiple of 8, the last at most W.  -> the table as a list of ints"""
+    cols = [int(c) for c in (block_col.tolist() if hasattr(block_col, "tolist") else block_col)]
+    if not 2 <= len(cols) <= 65:
+        raise L.KbnerError("gather_rows_blocks_drop failed with code -22: 1 to 64 blocks (got %d boundaries)" % len(cols))
+    if any(c % 8 for c in cols) or cols[0] < 0 or any(b < a for a, b in zip(cols, cols[1:])) or cols[-1] > int(W):
+        raise L.KbnerError("gather_rows_blocks_drop failed with code -22: block_col must be ascending multiples of 8 ending at or below "
+                           "W = %d (got %s)" % (int(W), cols))
+    return cols
+
+
+def gather_rows_blocks_drop(store, idx, block_col, block_on, n, R_out=None, ld_out=None, W=None, drop_e=NO_DROP, drop_l=NO_DROP, out=None):
+    """The head's padded input assembled from stored feature rows (include/kbner.h): store bf16 [*, ld_store], idx i32 [R = B * n] (-1 ->
+    zero row), block_on u8 [nblk] (device) -> out bf16 [R_out, ld_out], every element written: columns [0, W) of rows [0, R) hold
+    store[idx[r]] with the switched-off blocks zeroed and the two dropout sites of gather_rows_drop applied, everything else is 0.
+    block_col: the nblk + 1 column boundaries, as a HOST sequence (checked against the table contract here, then uploaded) or as a
+    device i32 tensor that check_block_cols has seen."""
+    _chk(store, BF16, "store"); _chk(idx, I32, "idx")
+    if store.dim() != 2 or block_on.dtype != torch.uint8 or not block_on.is_contiguous():
+        raise L.KbnerError("gather_rows_blocks_drop: store bf16 [*, ld_store], block_on contiguous uint8 [nblk]")
+    ld_store = store.shape[-1]
+    W = ld_store if W is None else int(W)
+    if not (torch.is_tensor(block_col) and block_col.device.type != "cpu"):
+        block_col = torch.tensor(check_block_cols(block_col, W), dtype=I32, device=store.device)
+    _chk(block_col, I32, "block_col")
+    nblk = block_col.numel() - 1
+    R, n = idx.numel(), int(n)
+    R_out = R if R_out is None else int(R_out)
+    if out is None:
+        out = torch.empty((R_out, W if ld_out is None else int(ld_out)), dtype=BF16, device=store.device)
+    else:
+        _chk(out, BF16, "out")
+    ld_out = out.shape[-1]
+    if out.dim() != 2 or out.shape[0] < R_out or block_on.numel() != nblk or not 1 <= nblk <= 64:
+        raise L.KbnerError("gather_rows_blocks_drop failed with code -22: out bf16 [>= R_out, ld_out], block_on [nblk], 1 <= nblk <= 64")
+    (se, te), (sl, tl) = drop_e, drop_l
+    L.call("kbner_gather_rows_blocks_drop", ptr(store), ld_store, ptr(idx), ptr(block_col), ptr(block_on), nblk, ptr(out), ld_out, R,
+           R_out, W, n, int(se) & 0xFFFFFFFF, int(te), int(sl) & 0xFFFFFFFF, int(tl), stream_ptr())
+    return out
+
+
 def gather_rows_layers(srcs, idx, n, mean=False, drop_e=NO_DROP, drop_l=NO_DROP, out=None):
     """The token features of an encoder layer selection: srcs = k bf16 [*, H] hidden states (1 <= k <= 32), idx i32 [B * n] (-1 ->
     zero row).  mean=False: the k selected rows side by side, bf16 [R, k * H] (k * H <= 8192); mean=True: their mean, bf16 [R, H].

@@ -12,7 +12,8 @@ embeddings.py:2469-2543, flair/models/language_model.py:71-138).
 Layout: ONE bf16 matrix X [rows = B * n padded to 128, D_total padded to 64] is the concatenation; every producer writes its own
 column block in place (transformers: kbner_gather_rows_ld from the encoder's hidden states; character LMs: the LSTM step
 kernel stores h_t at the token-end steps straight into X), so torch.cat never happens.  The BiLSTM's input half is one MFMA
-GEMM over all time steps, its recurrent half one launch per time step for both directions (csrc/lstm.hip)."""
+GEMM over all time steps, its recurrent half one launch per time step for both directions (csrc/lstm.hip).  While the head trains, the
+features are constants: FeatureStore keeps each sentence's rows of X after their first computation (embeddings_storage_mode)."""
 import numpy as np
 import torch
 
@@ -340,9 +341,10 @@ class BiLSTMHead:
         te, tl = ops.drop_thresh(self.dropout), ops.drop_thresh(self.locked_dropout)
         return word, ((int(sd[0]), te), (int(sd[1]), tl)), ((int(sd[2]), te), (int(sd[3]), tl))
 
-    def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw"):
+    def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw", source=None):
         """One micro-batch of head training on constant features: forward, CRF NLL, and loss_scale * its gradient ADDED to self.g.
-        X bf16 [rows, Dp] as new_input() lays it out; batch: the device dict of kbner.batch (ctags i32 [B, nc], clens i32 [B],
+        X bf16 [rows, Dp] as new_input() lays it out -- or None with `source`, a FeatureStore.source() of the batch: the first stage
+        (the pre-RNN dropouts and the padding to Dq) is then one kbner_gather_rows_blocks_drop from the stored rows; batch: the device dict of kbner.batch (ctags i32 [B, nc], clens i32 [B],
         cfeat_idx i32 [B * nc]: the S-X compaction of the emissions); weights f32 [B] replace the 1 / B of the batch mean.
         Sequence (sequence_tagger_model.py:959-964,969-994,1027 and the CRF loss): the three pre-RNN dropouts as one
         gather_rows_drop over X with an identity index (WordDropout: index -1), input GEMM, kbner_lstm_seq_train, the two post-RNN
@@ -352,24 +354,29 @@ class BiLSTMHead:
             raise L_.KbnerError("this BiLSTMHead was not built for training (enable_training())")
         with L_.stream_scope():
             dev, Hp, T, R = self.device, self.Hp, self.T, B * n
-            Mp = X.shape[0]
+            Mp = self.rows(B, n) if source is not None else X.shape[0]
             sites = self._draw_dropout(n) if drop == "draw" else drop
             self.last_drop = sites
             ident = None
             if sites is not None:
                 word, pre, post = sites
                 ident = torch.arange(R, dtype=I32, device=dev)
-                idx = ident
-                if word is not None:
-                    idx = torch.where(torch.from_numpy(np.tile(word, B)).to(dev), torch.full_like(ident, -1), ident)
-                Xd = torch.zeros((Mp, self.Dp), dtype=BF16, device=dev)
-                ops.gather_rows_drop(X, idx, n, pre[0], pre[1], out=Xd)
-                X = Xd
-            if self.Dq != self.Dp:
-                Xt = torch.zeros((Mp, self.Dq), dtype=BF16, device=dev)
-                Xt[:, :self.Dp] = X
+            if source is not None:
+                # the whole first stage as ONE launch from the stored rows: Xt [Mp, Dq] written whole (padding rows and columns too)
+                Xt = FeatureStore.launch(source, Mp, self.Dq, None if sites is None else (word, pre[0], pre[1]))
             else:
-                Xt = X
+                if sites is not None:
+                    idx = ident
+                    if word is not None:
+                        idx = torch.where(torch.from_numpy(np.tile(word, B)).to(dev), torch.full_like(ident, -1), ident)
+                    Xd = torch.zeros((Mp, self.Dp), dtype=BF16, device=dev)
+                    ops.gather_rows_drop(X, idx, n, pre[0], pre[1], out=Xd)
+                    X = Xd
+                if self.Dq != self.Dp:
+                    Xt = torch.zeros((Mp, self.Dq), dtype=BF16, device=dev)
+                    Xt[:, :self.Dp] = X
+                else:
+                    Xt = X
             gx = torch.empty((Mp, 8 * Hp), dtype=BF16, device=dev)
             ops.gemm(GEMM_NT, Xt, self.wih_t, Mp, 8 * Hp, self.Dq, C=gx, bias=self.bias, epi=EPI_BIAS)
             out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
@@ -421,6 +428,212 @@ class BiLSTMHead:
             ops.colsum(dgx, self.grad("bias_ih"))
             ops.colsum(dgx, self.grad("bias_hh"))
         return loss[0]
+
+
+class FeatureStore:
+    """The frozen features of the stacked tagger, computed once (flair's `embeddings_storage_mode`, training_utils.store_embeddings:
+    the reference keeps every embedding's vectors on the tokens after their first computation; here they are rows of ONE matrix).
+    Compact bf16 rows [tokens, Dp] in the head's column layout, one contiguous run of len(sentence) rows per sentence, keyed by the
+    sentence object (the store holds a reference, so an id is never reused).  A stored sentence's features are the bits of its FIRST
+    computation, in the batch it was first seen in.
+
+        mode "gpu": one device matrix, grown in steps of CHUNK_ROWS rows (growing copies the rows in use: old and new matrix exist
+                    together for the length of that copy); budget MAX_FRACTION of the free device memory at opening
+        mode "cpu": pinned host chunks of CHUNK_ROWS rows (budget: MAX_FRACTION of the free host memory); a batch's rows are gathered
+                    on the host into one pinned staging buffer and copied to the device on the current stream (non-blocking)
+
+    Reading is ONE launch of kbner_gather_rows_blocks_drop: padding rows (index -1), the embedding selection (block_on) and the
+    head's pre-RNN dropouts on the way out, into the padded matrix the consumer asks for.  The store remembers which column blocks
+    were computed when it was filled (`have`: the embedding selection in force then); a later selection that is a subset is served
+    by block_on, one that needs a missing block empties the store.  A batch with any sentence missing is not served (the caller
+    recomputes it whole); at the budget the store stops accepting sentences."""
+    MAX_FRACTION = 0.5
+    CHUNK_ROWS = 16384
+
+    def __init__(self, mode, Dp, block_col, device, budget_bytes=None):
+        if mode not in ("gpu", "cpu"):
+            raise ValueError("FeatureStore mode must be 'gpu' or 'cpu' (got %r; 'none' is: no store)" % (mode,))
+        self.mode, self.Dp, self.device = mode, int(Dp), torch.device(device)
+        self.block_col_host = ops.check_block_cols(block_col, self.Dp)
+        self.nblk = len(self.block_col_host) - 1
+        self.block_col = torch.tensor(self.block_col_host, dtype=I32, device=self.device)
+        if budget_bytes is None:
+            if mode == "gpu":
+                budget_bytes = self.MAX_FRACTION * torch.cuda.mem_get_info(self.device)[0]
+            else:
+                import os
+                budget_bytes = self.MAX_FRACTION * os.sysconf("SC_AVPHYS_PAGES") * os.sysconf("SC_PAGE_SIZE")
+        self.budget_rows = int(budget_bytes) // (2 * self.Dp)
+        self.pin = self.device.type == "cuda"
+        self.hits = self.misses = 0
+        self._staging = self._staged = None
+        self._warned = set()
+        self.want = [True] * self.nblk
+        self.block_on = torch.ones(self.nblk, dtype=torch.uint8, device=self.device)
+        self.clear()
+
+    # ---- bookkeeping
+    def clear(self):
+        self.index = {}            # id(sentence) -> (sentence, chunk, first row, rows)
+        self.chunks = []           # "gpu": at most one matrix [capacity, Dp]; "cpu": pinned host chunks [>= CHUNK_ROWS, Dp]
+        self.rows = 0              # rows stored
+        self._used = 0             # rows in use in the last chunk
+        self.have = None
+        self.full = False
+
+    close = clear
+
+    @property
+    def nbytes(self):
+        return self.rows * self.Dp * 2
+
+    def __len__(self):
+        return len(self.index)
+
+    def _log_once(self, key, msg, *args):
+        if key not in self._warned:
+            self._warned.add(key)
+            import logging
+            logging.getLogger("flair").info(msg, *args)
+
+    def select(self, on):
+        """the embedding selection of the next reads and writes: one bool per block.  A block the store lacks empties it."""
+        on = [bool(x) for x in on]
+        if len(on) != self.nblk:
+            raise ValueError("FeatureStore.select: one switch per block (%d)" % self.nblk)
+        if self.have is not None and any(o and not h for o, h in zip(on, self.have)):
+            import logging
+            logging.getLogger("flair").info("feature store: the selection needs a block that was not stored; %d sentences dropped, "
+                                            "the store refills", len(self.index))
+            self.clear()
+        if on != self.want:
+            self.want = on
+            self.block_on = torch.tensor([1 if o else 0 for o in on], dtype=torch.uint8, device=self.device)
+
+    def lookup(self, sentences):
+        """-> [(chunk, first row, rows)] per sentence, or None when any of them is missing"""
+        out = []
+        for s in sentences:
+            e = self.index.get(id(s))
+            if e is None:
+                self.misses += 1
+                return None
+            out.append(e[1:])
+        self.hits += 1
+        return out
+
+    # ---- writing
+    def _room(self, rows):
+        """-> (chunk, first row) of `rows` free contiguous rows, or None at the budget"""
+        if self.mode == "gpu":
+            cap = self.chunks[0].shape[0] if self.chunks else 0
+            if self.rows + rows > cap:
+                new = min(_round_up(self.rows + rows, self.CHUNK_ROWS), self.budget_rows)
+                if new < self.rows + rows:
+                    return None
+                grown = torch.empty((new, self.Dp), dtype=BF16, device=self.device)
+                if self.rows:
+                    grown[:self.rows] = self.chunks[0][:self.rows]
+                self.chunks = [grown]
+            return 0, self.rows
+        if not self.chunks or self._used + rows > self.chunks[-1].shape[0]:
+            # a batch's rows never straddle two chunks: the rest of the last one stays unused
+            size = max(self.CHUNK_ROWS, rows)
+            if sum(c.shape[0] for c in self.chunks) + size > self.budget_rows:
+                return None
+            self.chunks.append(torch.empty((size, self.Dp), dtype=BF16, pin_memory=self.pin))
+            self._used = 0
+        return len(self.chunks) - 1, self._used
+
+    def add(self, sentences, X, lengths, n):
+        """pack the real-token rows of a freshly computed X bf16 [rows, Dp] (token-major rows b * n + t) into the store: one
+        kbner_gather_rows_ld per batch.  Only whole batches computed under the selection the store was filled with are taken."""
+        if self.full:
+            return False
+        if self.have is not None and self.want != self.have:
+            self._log_once("subset", "feature store: a batch computed under a narrower selection than the stored one is not stored")
+            return False
+        new = [(b, s) for b, s in enumerate(sentences) if id(s) not in self.index]
+        total = sum(int(lengths[b]) for b, _ in new)
+        if not new or total == 0:
+            return False
+        at = self._room(total)
+        if at is None:
+            self.full = True
+            self._log_once("full", "feature store (%s): budget of %d rows reached at %d sentences; later sentences are recomputed",
+                           self.mode, self.budget_rows, len(self.index))
+            return False
+        chunk, r0 = at
+        src = np.concatenate([b * n + np.arange(int(lengths[b])) for b, _ in new]).astype(np.int32)
+        idx = torch.from_numpy(src).to(self.device)
+        if self.mode == "gpu":
+            ops.gather_rows_into(X, idx, self.chunks[0][r0:r0 + total], 0, self.Dp)
+        else:
+            packed = torch.empty((total, self.Dp), dtype=BF16, device=self.device)
+            ops.gather_rows_into(X, idx, packed, 0, self.Dp)
+            self.chunks[chunk][r0:r0 + total].copy_(packed)      # (blocking: the first visit of a sentence only)
+        off = r0
+        for b, s in new:
+            self.index[id(s)] = (s, chunk, off, int(lengths[b]))
+            off += int(lengths[b])
+        self._used = off
+        self.rows += total
+        self.have = list(self.want)
+        return True
+
+    # ---- reading
+    def source(self, sentences, n):
+        """what one launch of kbner_gather_rows_blocks_drop reads for this batch: {"store": bf16 [*, Dp] on the device, "idx": host
+        int32 [B * n] (-1 at padding positions), "block_col", "block_on", "n"} -- or None when a sentence is missing"""
+        found = self.lookup(sentences)
+        if found is None:
+            return None
+        B = len(found)
+        idx = np.full((B, n), -1, np.int32)
+        if self.mode == "gpu":
+            for b, (_, r0, rows) in enumerate(found):
+                idx[b, :rows] = np.arange(r0, r0 + rows)
+            store = self.chunks[0]
+        else:
+            total = sum(rows for _, _, rows in found)
+            if self._staging is None or self._staging.shape[0] < total:
+                cap = _round_up(max(total, 1), 1024)
+                self._staging = torch.empty((cap, self.Dp), dtype=BF16, pin_memory=self.pin)
+                self._staged = None
+            if self._staged is not None:
+                self._staged.synchronize()      # the previous batch's copy has left the staging buffer
+            off = 0
+            for b, (chunk, r0, rows) in enumerate(found):
+                self._staging[off:off + rows] = self.chunks[chunk][r0:r0 + rows]
+                idx[b, :rows] = np.arange(off, off + rows)
+                off += rows
+            store = torch.empty((max(total, 1), self.Dp), dtype=BF16, device=self.device)
+            store[:total].copy_(self._staging[:total], non_blocking=True)
+            if self.pin:
+                self._staged = torch.cuda.Event()
+                self._staged.record()
+        return {"store": store, "idx": idx.reshape(-1), "block_col": self.block_col, "block_on": self.block_on, "n": int(n)}
+
+    @staticmethod
+    def launch(source, R_out, ld_out, drop=None):
+        """one kbner_gather_rows_blocks_drop over a source -> bf16 [R_out, ld_out], every element written.  drop: None or (word: the
+        WordDropout positions, bool [n] or None -- folded into the index as -1 --, element site, locked site)"""
+        idx, n = source["idx"], source["n"]
+        site_e = site_l = ops.NO_DROP
+        if drop is not None:
+            word, site_e, site_l = drop
+            if word is not None:
+                idx = np.where(np.tile(np.asarray(word, bool), idx.size // n), np.int32(-1), idx).astype(np.int32)
+        store = source["store"]
+        return ops.gather_rows_blocks_drop(store, torch.from_numpy(idx).to(store.device), source["block_col"], source["block_on"], n,
+                                           R_out=R_out, ld_out=ld_out, drop_e=site_e, drop_l=site_l)
+
+    def assemble(self, sentences, n, out_ld, drop=None):
+        """the batch's matrix bf16 [B * n padded to 128, out_ld] from the store, or None when a sentence is missing"""
+        src = self.source(sentences, n)
+        if src is None:
+            return None
+        return self.launch(src, _round_up(max(len(sentences) * n, 1), 128), out_ld, drop)
 
 
 class StackOptimizer:
