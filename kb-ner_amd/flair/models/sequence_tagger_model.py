@@ -388,6 +388,29 @@ class SequenceTagger(flair.nn.Model):
             store.close()
         self._feature_store = None
 
+    def fill_feature_store(self, loaders):
+        """Compute every batch of `loaders` once with EVERY block on and store it (the reference embeds the whole corpus before the
+        first ACE episode, reinforcement_trainer.py:512-517): every later selection is then a subset of what the store holds and is
+        served by block_on, so a search never empties the store.  Nothing to do without an open store; sentences refused at the
+        store's budget are recomputed under the selection in force when they are read.  -> the number of batches computed"""
+        store = self.__dict__.get("_feature_store")
+        if store is None:
+            return 0
+        saved, computed = self.selection, 0
+        self.selection = None if saved is None else [1] * len(self._stack_embs)
+        try:
+            store.select([True] * store.nblk)
+            for loader in loaders:
+                for batch in loader:
+                    if store.full:
+                        return computed
+                    if any(id(s) not in store.index for s in batch):
+                        self._stack_compute(batch)
+                        computed += 1
+        finally:
+            self.selection = saved
+        return computed
+
     def _stack_selection(self):
         return self.selection if (getattr(self, "embedding_selector", False) and self.selection is not None) else None
 

@@ -33,6 +33,159 @@ def _warn_unknown(where, kwargs):
         log.warning("%s: ignoring unknown keyword(s) %s -- check the YAML for a misspelt key", where, ", ".join(extra))
 
 
+class _StackRun:
+    """The stacked tagger's epoch loop, the one copy that ModelFinetuner._train_stack (one run of epochs) and
+    ReinforcementTrainer.train (one run of epochs per episode) share: the loaders, training.log / loss.tsv, the feature store, the
+    optimizer with its schedule (`new_optimizer`), the epoch body (`epoch`: the shuffled batches, `gradient_accumulation_steps`
+    micro-batches of forward_backward per StackOptimizer.step, then the dev evaluations) and the plateau rule (`track`, `anneal`).
+    The shuffle generator, the head's dropout stream and the weights belong to the run, not to an optimizer: they carry over from
+    one `new_optimizer()` to the next."""
+
+    def __init__(self, trainer, base_path, a):
+        self.trainer, self.a, self.model = trainer, a, trainer.model
+        model = self.model
+        self.name = {"adamw": "AdamW", "sgd": "SGD"}.get(str(trainer.optimizer_name).lower(), str(trainer.optimizer_name))
+        base_path.mkdir(parents=True, exist_ok=True)
+        self.handler = add_file_handler(log, base_path / "training.log")
+        self.lr0, mbs = float(a["learning_rate"]), int(a["mini_batch_size"])
+        self.accum = accum = max(1, int(a["gradient_accumulation_steps"]))
+        self.eval_bs = a["eval_mini_batch_size"] or max(mbs, 32 if trainer.sentence_level_batch else mbs)
+        train_data = [s for ds in trainer.corpus.train_list for s in ds]
+        self.loader = ColumnDataLoader(train_data, mbs, a["shuffle"], use_bert=trainer.use_bert, tokenizer=trainer.bert_tokenizer,
+                                       model=model, sentence_level_batch=trainer.sentence_level_batch, sort_data=a["sort_data"])
+        self.loader.assign_tags(model.tag_type, model.tag_dictionary)
+        self.dev_loaders = []
+        for ds in trainer.corpus.dev_list:
+            dl = ColumnDataLoader(list(ds), self.eval_bs, False, sort_data=a["sort_data"], model=model,
+                                  sentence_level_batch=trainer.sentence_level_batch)
+            dl.assign_tags(model.tag_type, model.tag_dictionary)
+            self.dev_loaders.append(dl)
+        if not self.dev_loaders or not any(len(d) for d in self.dev_loaders):
+            raise NotImplementedError("the stacked tagger (use_rnn: true) needs a dev set to select stack-model.pt by")
+        self.head = model.enable_stack_training()
+        steps_epoch = (len(self.loader) + accum - 1) // accum
+        self.t_total = steps_epoch * int(a["max_epochs"])
+        self.warmup = steps_epoch * int(a["warmup_epochs"]) if a["use_warmup"] else int(a["warmup_steps"])
+        self.linear = bool(a["fine_tune_mode"])
+        self.opt = None
+        log_line(log)
+        log.info('Model: "frozen stacked embeddings + BiLSTM + linear + CRF on kbner HIP engine", tags=%d, optimizer %s',
+                 len(model.tag_dictionary), self.name)
+        log.info('Parameters: learning_rate "%s", lr_rate "%s", mini_batch_size "%s", accumulate "%s", max_epochs "%s", schedule "%s"',
+                 self.lr0, a["lr_rate"], mbs, accum, a["max_epochs"], "linear, warmup %d" % self.warmup if self.linear else "plateau")
+        log_line(log)
+        self.loss_txt = init_output_file(base_path, "loss.tsv")
+        with open(self.loss_txt, "a") as f:
+            f.write("EPOCH\tTIMESTAMP\tLEARNING_RATE\tTRAIN_LOSS\tDEV_LOSS\tDEV_F1\tDEV_MACRO_F1\n")
+        self.rng = random.Random(20220711)
+        self.order = list(range(len(self.loader)))
+        self.dev_score_history, self.dev_loss_history, self.train_loss_history = [], [], []
+        self.hook = getattr(trainer, "stack_step_hook", None)   # tests: called after every optimizer step with (its batches, their losses)
+        # embeddings_storage_mode (the reference keeps the frozen embeddings on the sentences after their first computation): "gpu" /
+        # "cpu" open the tagger's feature store, which training, the dev evaluations and final_test read; "none": no store
+        self.storage = str(a["embeddings_storage_mode"]).lower()
+        if self.storage not in ("none", "cpu", "gpu"):
+            raise ValueError("embeddings_storage_mode must be 'none', 'cpu' or 'gpu' (got %r)" % (a["embeddings_storage_mode"],))
+        self.store = model.open_feature_store(self.storage)
+
+    def linear_scale(self, t):
+        if t < self.warmup:
+            return float(t) / float(max(1, self.warmup))
+        return max(0.0, float(self.t_total - t) / float(max(1, self.t_total - self.warmup)))
+
+    def new_optimizer(self):
+        """a fresh StackOptimizer (moments and step count cleared) at the default learning rate: plateau factor 1, no bad epochs"""
+        from kbner.stack import StackOptimizer
+        self.opt = StackOptimizer(self.head, name=self.name, lr=self.lr0, lr_rate=float(self.a["lr_rate"]), max_norm=5.0)
+        self.model.stack_optimizer = self.trainer.optimizer = self.opt
+        self.plateau = 1.0
+        self.best_score, self.bad_epochs = -1.0, 0
+        return self.opt
+
+    def epoch(self, epoch):
+        """one epoch of training, then the dev evaluations -> the dev score (x100, averaged over the dev sets)"""
+        a, model, opt, loader, accum = self.a, self.model, self.opt, self.loader, self.accum
+        if a["shuffle"]:
+            self.rng.shuffle(self.order)
+        order = self.order
+        model.train()
+        tot, cnt, t_ep, seen = 0.0, 0, time.time(), 0
+        for g0 in range(0, len(order), accum):
+            group = order[g0:g0 + accum]
+            losses = []
+            for bi in group:
+                batch = loader[bi]
+                losses.append(model.forward_backward(batch, loss_scale=1.0 / len(group)))
+                seen += len(batch)
+                store_embeddings(batch, "none")
+            opt.lr_scale = self.linear_scale(opt.t) if self.linear else self.plateau
+            opt.step()
+            if self.hook is not None:
+                self.hook([loader[bi] for bi in group], losses)
+            tot += float(sum(losses)) / len(group)
+            cnt += 1
+        train_loss = tot / max(cnt, 1)
+        self.train_loss_history.append(train_loss)
+        model.trained_epochs = epoch + 1
+        model.eval()
+        lr_now = self.lr0 * (self.linear_scale(opt.t) if self.linear else self.plateau)
+        log_line(log)
+        log.info("EPOCH %d done: loss %.4f - lr %.2e - %.1f sentences/sec", epoch + 1, train_loss, lr_now, seen / max(time.time() - t_ep, 1e-9))
+        f1s, dls = [], []
+        for dname, dl in zip(getattr(self.trainer.corpus, "targets", ["dev"]), self.dev_loaders):
+            res, dl_loss = model.evaluate(dl, embeddings_storage_mode="none")
+            log.info("%s DEV : loss %.4f - f1 %.4f - macro %.4f", dname, dl_loss, res.main_score, res.macro_score)
+            f1s.append((res.macro_score if a["select_model_by_macro"] else res.main_score) * 100)
+            dls.append(dl_loss)
+        score = sum(f1s) / len(f1s)
+        self.dev_score_history.append(score)
+        self.dev_loss_history.append(sum(dls) / len(dls))
+        self.log_store()
+        with open(self.loss_txt, "a") as f:
+            f.write("%d\t%s\t%.3e\t%.6f\t%s\t%s\t_\n" % (epoch + 1, time.strftime("%H:%M:%S"), lr_now, train_loss, self.dev_loss_history[-1], score))
+        return score
+
+    def prefill(self):
+        """with a store open: every training and dev batch computed once, with every embedding on (fill_feature_store)"""
+        if self.store is not None:
+            n = self.model.fill_feature_store([self.loader] + self.dev_loaders)
+            log.info("feature store (%s) filled under the full selection: %d batches computed - %d sentences, %d rows, %d bytes",
+                     self.storage, n, len(self.store), self.store.rows, self.store.nbytes)
+
+    def log_store(self):
+        store = self.store
+        if store is not None:
+            log.info("feature store (%s): %d batches served, %d recomputed - %d sentences, %d rows, %d bytes", self.storage,
+                     store.hits, store.misses, len(store), store.rows, store.nbytes)
+
+    def track(self, score):
+        """the plateau rule's bookkeeping -> whether `score` is (a tie with) the best since new_optimizer()"""
+        if score > self.best_score:
+            self.best_score, self.bad_epochs = score, 0
+        else:
+            self.bad_epochs += 1
+        return score == self.best_score
+
+    def anneal(self, min_learning_rate=None):
+        """lr *= anneal_factor after `patience` + 1 epochs without a better dev score -> True: below min_learning_rate, stop"""
+        a = self.a
+        if not self.linear and self.bad_epochs > int(a["patience"]):
+            self.plateau *= float(a["anneal_factor"])
+            self.bad_epochs = 0
+            log.info("no better dev score for %d epochs: learning rate -> %.3e", int(a["patience"]) + 1, self.lr0 * self.plateau)
+            if self.lr0 * self.plateau < float(a["min_learning_rate"] if min_learning_rate is None else min_learning_rate):
+                log.info("learning rate below min_learning_rate: stopping")
+                return True
+        return False
+
+    def save_model(self, path):
+        torch.save(self.model._stack_state, str(path))
+
+    def close(self):
+        self.model.close_feature_store()
+        log.removeHandler(self.handler)
+
+
 class ModelFinetuner:
     def __init__(self, model: flair.nn.Model, teachers: List[flair.nn.Model], corpus, optimizer=None, professors=None,
                  epoch: int = 0, optimizer_state: dict = None, scheduler_state: dict = None, use_tensorboard: bool = False,
@@ -575,18 +728,10 @@ class ModelFinetuner:
         return {"test_score": final_score, "dev_score_history": dev_score_history, "train_loss_history": train_loss_history,
                 "dev_loss_history": dev_loss_history}
 
-    def _train_stack(self, base_path, a, kwargs):
-        """ModelFinetuner.train for a `use_rnn: true` model (frozen embeddings -> BiLSTM -> linear -> CRF).  One process.  Walks the
-        ColumnDataLoader batches, `gradient_accumulation_steps` micro-batches of forward_backward per optimizer step
-        (kbner.stack.StackOptimizer: AdamW, the default, or SGD by the trainer block's `optimizer`; `linear.*` at learning_rate,
-        `rnn.*` and `transitions` at learning_rate * lr_rate, finetune_trainer.py:552-571), evaluates on dev after every epoch and
-        writes the best dev score's weights to `stack-model.pt` (the reference-layout dict load_stack_state takes), training.log and
-        loss.tsv as the fine-tuning loop does.  Schedule: fine_tune_mode -> linear decay with warm-up (:672-688); otherwise the
-        plateau rule the reference uses off the fine-tune path (:1362-1390): lr *= anneal_factor after `patience` epochs without a
-        better dev score, stop below min_learning_rate."""
+    def _stack_refusals(self, a, kwargs):
+        """what the stacked tagger's single-process loop does not do, refused by name before any work"""
         from kbner import dp
-        from kbner.stack import StackOptimizer
-        _warn_unknown("ModelFinetuner.train", kwargs)
+        _warn_unknown("%s.train" % type(self).__name__, kwargs)
         if dp.world_size() > 1:
             raise NotImplementedError("WORLD_SIZE > 1: the stacked tagger (use_rnn: true) trains in one process")
         if self.distill_mode:
@@ -597,124 +742,40 @@ class ModelFinetuner:
             raise NotImplementedError("train_with_dev: the stacked tagger (use_rnn: true) selects stack-model.pt by the dev score")
         for flag in ("use_amp", "use_autocast", "rootschedule", "freezing", "use_unlabeled_data", "unlabeled_data_for_zeroshot",
                      "gold_reward", "language_attention_warmup", "language_attention_warmup_and_fix"):
-            if a[flag]:
+            if a.get(flag):
                 raise NotImplementedError("train(%s=...) selects a path outside the stacked tagger's training loop" % flag)
-        name = {"adamw": "AdamW", "sgd": "SGD"}.get(str(self.optimizer_name).lower(), str(self.optimizer_name))
-        model = self.model
-        base_path.mkdir(parents=True, exist_ok=True)
-        handler = add_file_handler(log, base_path / "training.log")
-        lr0, mbs, accum = float(a["learning_rate"]), int(a["mini_batch_size"]), max(1, int(a["gradient_accumulation_steps"]))
-        eval_bs = a["eval_mini_batch_size"] or max(mbs, 32 if self.sentence_level_batch else mbs)
-        train_data = [s for ds in self.corpus.train_list for s in ds]
-        loader = ColumnDataLoader(train_data, mbs, a["shuffle"], use_bert=self.use_bert, tokenizer=self.bert_tokenizer, model=model,
-                                  sentence_level_batch=self.sentence_level_batch, sort_data=a["sort_data"])
-        loader.assign_tags(model.tag_type, model.tag_dictionary)
-        dev_loaders = []
-        for ds in self.corpus.dev_list:
-            dl = ColumnDataLoader(list(ds), eval_bs, False, sort_data=a["sort_data"], model=model, sentence_level_batch=self.sentence_level_batch)
-            dl.assign_tags(model.tag_type, model.tag_dictionary)
-            dev_loaders.append(dl)
-        if not dev_loaders or not any(len(d) for d in dev_loaders):
-            raise NotImplementedError("the stacked tagger (use_rnn: true) needs a dev set to select stack-model.pt by")
-        head = model.enable_stack_training()
-        opt = StackOptimizer(head, name=name, lr=lr0, lr_rate=float(a["lr_rate"]), max_norm=5.0)
-        model.stack_optimizer = self.optimizer = opt
-        steps_epoch = (len(loader) + accum - 1) // accum
-        t_total = steps_epoch * int(a["max_epochs"])
-        warmup = steps_epoch * int(a["warmup_epochs"]) if a["use_warmup"] else int(a["warmup_steps"])
-        linear = bool(a["fine_tune_mode"])
 
-        def linear_scale(t):
-            if t < warmup:
-                return float(t) / float(max(1, warmup))
-            return max(0.0, float(t_total - t) / float(max(1, t_total - warmup)))
-        plateau = 1.0
-        log_line(log)
-        log.info('Model: "frozen stacked embeddings + BiLSTM + linear + CRF on kbner HIP engine", tags=%d, optimizer %s', len(model.tag_dictionary), name)
-        log.info('Parameters: learning_rate "%s", lr_rate "%s", mini_batch_size "%s", accumulate "%s", max_epochs "%s", schedule "%s"',
-                 lr0, a["lr_rate"], mbs, accum, a["max_epochs"], "linear, warmup %d" % warmup if linear else "plateau")
-        log_line(log)
-        loss_txt = init_output_file(base_path, "loss.tsv")
-        with open(loss_txt, "a") as f:
-            f.write("EPOCH\tTIMESTAMP\tLEARNING_RATE\tTRAIN_LOSS\tDEV_LOSS\tDEV_F1\tDEV_MACRO_F1\n")
-        rng = random.Random(20220711)
-        order = list(range(len(loader)))
-        best_score, bad_epochs = -1.0, 0
-        dev_score_history, dev_loss_history, train_loss_history = [], [], []
-        hook = getattr(self, "stack_step_hook", None)     # tests: called after every optimizer step with (its batches, their losses)
-        # embeddings_storage_mode (the reference keeps the frozen embeddings on the sentences after their first computation): "gpu" /
-        # "cpu" open the tagger's feature store, which training, the dev evaluations and final_test below read; "none": no store
-        storage = str(a["embeddings_storage_mode"]).lower()
-        if storage not in ("none", "cpu", "gpu"):
-            raise ValueError("embeddings_storage_mode must be 'none', 'cpu' or 'gpu' (got %r)" % (a["embeddings_storage_mode"],))
-        store = model.open_feature_store(storage)
+    def _train_stack(self, base_path, a, kwargs):
+        """ModelFinetuner.train for a `use_rnn: true` model (frozen embeddings -> BiLSTM -> linear -> CRF).  One process.  Walks the
+        ColumnDataLoader batches, `gradient_accumulation_steps` micro-batches of forward_backward per optimizer step
+        (kbner.stack.StackOptimizer: AdamW, the default, or SGD by the trainer block's `optimizer`; `linear.*` at learning_rate,
+        `rnn.*` and `transitions` at learning_rate * lr_rate, finetune_trainer.py:552-571), evaluates on dev after every epoch and
+        writes the best dev score's weights to `stack-model.pt` (the reference-layout dict load_stack_state takes), training.log and
+        loss.tsv as the fine-tuning loop does.  Schedule: fine_tune_mode -> linear decay with warm-up (:672-688); otherwise the
+        plateau rule the reference uses off the fine-tune path (:1362-1390): lr *= anneal_factor after `patience` epochs without a
+        better dev score, stop below min_learning_rate.  The epoch body is _StackRun's, which ReinforcementTrainer's episodes share."""
+        self._stack_refusals(a, kwargs)
+        run = _StackRun(self, base_path, a)
         try:
             try:
+                run.new_optimizer()
                 for epoch in range(self.epoch, int(a["max_epochs"])):
-                    if a["shuffle"]:
-                        rng.shuffle(order)
-                    model.train()
-                    tot, cnt, t_ep, seen = 0.0, 0, time.time(), 0
-                    for g0 in range(0, len(order), accum):
-                        group = order[g0:g0 + accum]
-                        losses = []
-                        for bi in group:
-                            batch = loader[bi]
-                            losses.append(model.forward_backward(batch, loss_scale=1.0 / len(group)))
-                            seen += len(batch)
-                            store_embeddings(batch, "none")
-                        opt.lr_scale = linear_scale(opt.t) if linear else plateau
-                        opt.step()
-                        if hook is not None:
-                            hook([loader[bi] for bi in group], losses)
-                        tot += float(sum(losses)) / len(group)
-                        cnt += 1
-                    train_loss = tot / max(cnt, 1)
-                    train_loss_history.append(train_loss)
-                    model.trained_epochs = epoch + 1
-                    model.eval()
-                    lr_now = lr0 * (linear_scale(opt.t) if linear else plateau)
-                    log_line(log)
-                    log.info("EPOCH %d done: loss %.4f - lr %.2e - %.1f sentences/sec", epoch + 1, train_loss, lr_now, seen / max(time.time() - t_ep, 1e-9))
-                    f1s, dls = [], []
-                    for dname, dl in zip(getattr(self.corpus, "targets", ["dev"]), dev_loaders):
-                        res, dl_loss = model.evaluate(dl, embeddings_storage_mode="none")
-                        log.info("%s DEV : loss %.4f - f1 %.4f - macro %.4f", dname, dl_loss, res.main_score, res.macro_score)
-                        f1s.append((res.macro_score if a["select_model_by_macro"] else res.main_score) * 100)
-                        dls.append(dl_loss)
-                    score = sum(f1s) / len(f1s)
-                    dev_score_history.append(score)
-                    dev_loss_history.append(sum(dls) / len(dls))
-                    if store is not None:
-                        log.info("feature store (%s): %d batches served, %d recomputed - %d sentences, %d rows, %d bytes", storage,
-                                 store.hits, store.misses, len(store), store.rows, store.nbytes)
-                    with open(loss_txt, "a") as f:
-                        f.write("%d\t%s\t%.3e\t%.6f\t%s\t%s\t_\n" % (epoch + 1, time.strftime("%H:%M:%S"), lr_now, train_loss, dev_loss_history[-1], score))
-                    if score > best_score:
-                        best_score, bad_epochs = score, 0
-                    else:
-                        bad_epochs += 1
-                    if score == best_score:
+                    score = run.epoch(epoch)
+                    if run.track(score):
                         log.info("==================Saving the current best model: %s==================", score)
-                        torch.save(model._stack_state, str(base_path / "stack-model.pt"))
-                    if not linear and bad_epochs > int(a["patience"]):
-                        plateau *= float(a["anneal_factor"])
-                        bad_epochs = 0
-                        log.info("no better dev score for %d epochs: learning rate -> %.3e", int(a["patience"]) + 1, lr0 * plateau)
-                        if lr0 * plateau < float(a["min_learning_rate"]):
-                            log.info("learning rate below min_learning_rate: stopping")
-                            break
+                        run.save_model(base_path / "stack-model.pt")
+                    if run.anneal():
+                        break
             except KeyboardInterrupt:
                 log_line(log)
                 log.info("Exiting from training early.")
             final_score = 0.0
             if self.corpus.test is not None and len(self.corpus.test) > 0:
-                final_score = self.final_test(base_path, eval_bs, quiet_mode=False)
+                final_score = self.final_test(base_path, run.eval_bs, quiet_mode=False)
         finally:
-            model.close_feature_store()
-        log.removeHandler(handler)
-        return {"test_score": final_score, "dev_score_history": dev_score_history, "train_loss_history": train_loss_history,
-                "dev_loss_history": dev_loss_history}
+            run.close()
+        return {"test_score": final_score, "dev_score_history": run.dev_score_history, "train_loss_history": run.train_loss_history,
+                "dev_loss_history": run.dev_loss_history}
 
     def save_finetuned_embedding(self, base_path):
         """write `<base_path>/<basename of the embedding dir>/` with tokenizer + current encoder weights, the directory the

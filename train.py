@@ -8,9 +8,12 @@
     torchrun --nproc-per-node 8 train.py --config ...                # data-parallel over RCCL (new capability)
 
 The reference's own train.py also runs unchanged against this package (put kb-ner_amd/ on PYTHONPATH): it only needs the
-flair.* import surface listed in SURVEY.md §8b.  --predict_posterior (marginal decoding), --v2doc (document-window context)
-and, for `trainer: ReinforcementTrainer` YAMLs (the ACE stack), --test / --parse with the controller's `best_action` from
-training_state.pt are supported; modes outside the hot path (--zeroshot/--all/--other/--predict/--mst/...) are rejected."""
+flair.* import surface listed in SURVEY.md §8b.  --predict_posterior (marginal decoding) and --v2doc (document-window context)
+are supported.  A `trainer: ReinforcementTrainer` YAML (the ACE stack) trains the controller's search over embedding subsets
+(ReinforcementTrainer.train); --test / --parse then read the controller's `best_action` from training_state.pt and the head from
+stack-model.pt.  A YAML whose `embeddings:` block lists ELMo / fastText placeholders can be tested and parsed (deselected) but not
+trained: the refusal is printed and the exit status is non-zero.  Modes outside the hot path
+(--zeroshot/--all/--other/--predict/--mst/...) are rejected."""
 import argparse
 import logging
 import os
@@ -66,8 +69,6 @@ def main():
     if trainer_name not in ("ModelFinetuner", "ReinforcementTrainer"):
         sys.exit("trainer %s is outside the hot path" % trainer_name)
     inference = args.test or args.parse or args.parse_test or args.test_speed
-    if trainer_name == "ReinforcementTrainer" and not inference:
-        sys.exit("ReinforcementTrainer (ACE) YAMLs are supported for --test / --parse only: training the controller is out of scope")
     tcfg = dict(cp.config.get(trainer_name, {}))
     tcfg.setdefault("distill_mode", False)
     if tcfg["distill_mode"] and not inference and trainer_name == "ModelFinetuner":
@@ -91,7 +92,7 @@ def main():
         for e in embs:
             if hasattr(e, "v2_doc"):
                 e.v2_doc = True
-    if trainer_name == "ReinforcementTrainer":
+    if trainer_name == "ReinforcementTrainer" and inference:
         # train.py:214-218: the embedding subset the controller settled on; the stack's own weights come from stack-model.pt
         # ({"rnn": LSTM state dict, "linear.weight", "linear.bias", "transitions"}; INTEGRATION.md shows the two-line export to
         # run next to the reference's checkpoint -- its .pt pickles the reference's classes and cannot be read here)
@@ -135,6 +136,15 @@ def main():
             res, _ = student.evaluate(loader, out_path=out_dir / ("%s%s.conllu" % (name, args.parse_name)),
                                       embeddings_storage_mode="none", prediction_mode=True)
             print(name, res.log_line)
+        return
+    if trainer_name == "ReinforcementTrainer":
+        # the ACE search: every episode trains the stacked tagger's head under the controller's action (writes stack-model.pt,
+        # controller.pt, training_state.pt, curriculum.json -- what --test / --parse above read).  What the search does not do
+        # (placeholder embeddings in the YAML, the sentence-level controller, ...) is refused by name before any work
+        try:
+            trainer.train(base_path, **train_config)
+        except NotImplementedError as e:
+            sys.exit("ReinforcementTrainer: %s" % e)
         return
     trainer.train(base_path, **train_config)
 
