@@ -210,6 +210,26 @@ int kbner_gather_rows_layers(const kbner_bf16* const* srcs, int k, int mean, con
  * ld = H, scale = 1/k.  ld % 8 == 0, col0 % 8 == 0, col0 + H <= ld. */
 int kbner_scatter_add_rows_ld(const kbner_bf16* dout, int ld, int col0, const int* idx, kbner_bf16* dst, int R, int H, float scale,
                               int n, uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+/* Sub-token pooling of a FROZEN TransformerWordEmbeddings in the stacked tagger (pooling_operation first / last / first_last / mean over
+ * any layer selection, with or without use_scalar_mix): the per-token, per-layer slice / [0] / [-1] / torch.cat / torch.mean loop of
+ * flair/embeddings.py:3303-3345 (the seam stitching of :3292-3299 is folded into the row table) and the torch.cat of the embedding's
+ * features into the tagger's input (sequence_tagger_model.py:879-891), as ONE segmented row reduction, forward only.
+ * srcs: HOST array of k device pointers (1 <= k <= 32), each a bf16 [*, H] hidden state with row stride H, as for
+ * kbner_gather_rows_layers.  span_ptr i32 [R + 1] (DEVICE), non-decreasing, span_ptr[0] == 0; span_rows i32 [span_ptr[R]] (DEVICE): the
+ * encoder-matrix rows of word r's sub-tokens, in order, at span_rows[span_ptr[r] .. span_ptr[r + 1]) -- they need not be consecutive.
+ * op: 0 first, 1 last, 2 first_last, 3 mean.  With m = span_ptr[r + 1] - span_ptr[r] and rows = word r's entries, per layer j:
+ *   first     : p_j = src_j[rows[0]]                               Wp = H
+ *   last      : p_j = src_j[rows[m - 1]]                           Wp = H
+ *   first_last: p_j = [src_j[rows[0]], src_j[rows[m - 1]]]         Wp = 2 H
+ *   mean      : p_j = (sum_t src_j[rows[t]], fp32, t ascending) * fp32(1 / m)       Wp = H     (no intermediate bf16 rounding)
+ *   layer_mean == 0: out[r, 0:W] = p_0 .. p_{k-1} side by side, W = k * Wp
+ *   layer_mean != 0: out[r, 0:W] = (sum_j p_j, fp32, j ascending) * fp32(1 / k), W = Wp
+ * ONE rounding (to nearest even) to bf16, at the store; first / last / first_last with layer_mean == 0 copy (the output bits are the
+ * source bits).  m == 0 (a word the tokenizer dropped, :3306-3308): W zeros.  Only columns [0, W) of rows [0, R) are written, at row
+ * stride ld_out -- out points at the embedding's column block; the neighbouring blocks are not touched.  H % 8 == 0, ld_out % 8 == 0,
+ * out 16-byte aligned, W <= ld_out, else -22.  (The table conditions live in device memory: kbner.ops checks them on the host copy.) */
+int kbner_pool_rows_layers(const kbner_bf16* const* srcs, int k, int layer_mean, int op, const int* span_ptr, const int* span_rows,
+                           kbner_bf16* out, int ld_out, int R, int H, void* stream);
 /* self.linear, sequence_tagger_model.py:1027: out f32[R,T] = x bf16[R,H] . w f32[T,H]^T + bias; T <= 192 (bwd_dw walks the tags in
  * blocks of 64 above 64 tags); H <= 8192 (rows wider than 1024 columns are walked in 512-column chunks) */
 int kbner_head_fwd(const kbner_bf16* x, const float* w, const float* bias, float* out, int R, int H, int T, void* stream);

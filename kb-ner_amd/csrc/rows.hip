@@ -161,6 +161,80 @@ __global__ __launch_bounds__(256) void gather_rows_layers_kernel(const LayerSrcs
   }
 }
 
+// Sub-token pooling of a FROZEN encoder's hidden states (TransformerWordEmbeddings(pooling_operation=..., layers=..., use_scalar_mix=...)
+// in the stacked tagger, flair/embeddings.py:3303-3345): word r owns the encoder-matrix rows span_rows[span_ptr[r] .. span_ptr[r + 1])
+// -- its sub-tokens in order, not necessarily consecutive (a word may straddle a sliding-window seam) -- and its feature is a segmented
+// reduction of those rows over k hidden states, written straight into the embedding's column block of the stack's input matrix
+// (row stride ld_out; only columns [0, W) of rows [0, R) are written).  With m = the span's length, per layer j:
+//     first: p_j = src_j[rows[0]]     last: p_j = src_j[rows[m - 1]]     first_last: p_j = [src_j[rows[0]], src_j[rows[m - 1]]]  (2 H wide)
+//     mean : p_j = (sum over the span in order, fp32) * fp32(1 / m)
+// and the row is p_0 .. p_{k-1} side by side or, LMEAN, (sum_j p_j, fp32, j ascending) * fp32(1 / k); ONE rounding to bf16, at the
+// store.  m == 0 (a word the tokenizer dropped, :3306-3308): zeros.  first / last / first_last without LMEAN copy: the output bits are
+// the source bits.  Same shape as gather_rows_layers_kernel: one wave per row, 16-byte accesses, the 512-column chunk of the OUTPUT row
+// as the outer loop, so the chunk's layer, half and source column stay in registers over the rows (H % 8 == 0: an 8-column group lies in
+// one layer and one half); span bounds and row numbers are wave-uniform.
+#define POOL_FIRST 0
+#define POOL_LAST 1
+#define POOL_FIRST_LAST 2
+#define POOL_MEAN 3
+template <int OP, bool LMEAN>
+__global__ __launch_bounds__(256) void pool_rows_layers_kernel(const LayerSrcs srcs, int k, const int* __restrict__ span_ptr,
+                                                               const int* __restrict__ span_rows, bf16_t* __restrict__ out, int ld_out,
+                                                               int R, int H) {
+  const int lane = threadIdx.x % 64;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + threadIdx.x / 64);
+  const int nwave = gridDim.x * 4;
+  const int Wp = OP == POOL_FIRST_LAST ? 2 * H : H;
+  const int W = LMEAN ? Wp : k * Wp;
+  const int nj = LMEAN ? k : 1;
+  const float inv_k = 1.0f / (float)k;
+  for (int c0 = lane * 8; c0 < W; c0 += 512) {
+    const int j0 = LMEAN ? 0 : c0 / Wp;
+    const int cp = LMEAN ? c0 : c0 % Wp;
+    const bool tail = OP == POOL_LAST || (OP == POOL_FIRST_LAST && cp >= H);
+    const int h0 = (OP == POOL_FIRST_LAST && cp >= H) ? cp - H : cp;
+    for (int r = wave; r < R; r += nwave) {
+      const int lo = __builtin_amdgcn_readfirstlane(span_ptr[r]);
+      const int hi = __builtin_amdgcn_readfirstlane(span_ptr[r + 1]);
+      uint4 u = make_uint4(0, 0, 0, 0);
+      if (hi > lo) {
+        if (OP != POOL_MEAN && !LMEAN) {
+          const int s = span_rows[tail ? hi - 1 : lo];
+          u = *reinterpret_cast<const uint4*>(srcs.p[j0] + (size_t)s * H + h0);
+        } else {
+          const float inv_m = 1.0f / (float)(hi - lo);
+          float acc[8];
+          for (int q = 0; q < nj; ++q) {
+            const bf16_t* __restrict__ src = srcs.p[j0 + q];
+            float p[8];
+            if (OP == POOL_MEAN) {
+              unpack8bf(*reinterpret_cast<const uint4*>(src + (size_t)span_rows[lo] * H + h0), p);
+              for (int t = lo + 1; t < hi; ++t) {
+                float x[8];
+                unpack8bf(*reinterpret_cast<const uint4*>(src + (size_t)span_rows[t] * H + h0), x);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) p[i] += x[i];
+              }
+#pragma unroll
+              for (int i = 0; i < 8; ++i) p[i] *= inv_m;
+            } else {
+              unpack8bf(*reinterpret_cast<const uint4*>(src + (size_t)span_rows[tail ? hi - 1 : lo] * H + h0), p);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = q == 0 ? p[i] : acc[i] + p[i];
+          }
+          if (LMEAN) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] *= inv_k;
+          }
+          u = pack8bf(acc);
+        }
+      }
+      *reinterpret_cast<uint4*>(out + (size_t)r * ld_out + c0) = u;
+    }
+  }
+}
+
 // The backward of one source's share: columns [col0, col0 + H) of the W-wide feature gradient (row stride ld) are ADDED to the rows of
 // that source's gradient idx names -- added, because the matrix already holds what the layers above sent down:
 //     dst[idx[r], h] = bf16(f32(dst[idx[r], h]) + f32(dout[r * ld + col0 + h]) * (m[r, col0 + h] * scale))      for idx[r] >= 0
@@ -371,6 +445,39 @@ int kbner_gather_rows_layers(const bf16_t* const* srcs, int k, int mean, const i
   else if (drop) LAYERS_LAUNCH(false, true);
   else LAYERS_LAUNCH(false, false);
 #undef LAYERS_LAUNCH
+  KBNER_LAUNCH_RET();
+}
+
+// srcs: HOST array of k device pointers, as above; span_ptr i32 [R + 1], span_rows i32 [span_ptr[R]]: DEVICE memory.  What the tables
+// must hold (span_ptr non-decreasing from 0, every span_rows entry a row of every source) cannot be checked here; kbner.ops checks the
+// host copy before it uploads them.
+int kbner_pool_rows_layers(const bf16_t* const* srcs, int k, int layer_mean, int op, const int* span_ptr, const int* span_rows,
+                           bf16_t* out, int ld_out, int R, int H, void* stream) {
+  KBNER_CHECK_ARG(srcs != nullptr && k >= 1 && k <= LAYERS_MAX && op >= POOL_FIRST && op <= POOL_MEAN && R >= 0 && H > 0 && H % 8 == 0);
+  KBNER_CHECK_ARG(ld_out > 0 && ld_out % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0);
+  const long long W = (long long)(op == POOL_FIRST_LAST ? 2 : 1) * H * (layer_mean ? 1 : k);
+  KBNER_CHECK_ARG(W <= ld_out);
+  LayerSrcs b;
+  for (int i = 0; i < LAYERS_MAX; ++i) {
+    b.p[i] = srcs[i < k ? i : 0];
+    KBNER_CHECK_ARG(b.p[i] != nullptr);
+  }
+  if (R == 0) return 0;
+  KBNER_CHECK_ARG(span_ptr != nullptr && span_rows != nullptr && out != nullptr);
+#define POOL_LAUNCH(OP, LMEAN)                                                                                                      \
+  hipLaunchKernelGGL((pool_rows_layers_kernel<OP, LMEAN>), dim3(rows_grid(R)), dim3(256), 0, (hipStream_t)stream, b, k, span_ptr,  \
+                     span_rows, out, ld_out, R, H)
+#define POOL_LAUNCH_OP(OP)            \
+  do {                                \
+    if (layer_mean) POOL_LAUNCH(OP, true); \
+    else POOL_LAUNCH(OP, false);      \
+  } while (0)
+  if (op == POOL_FIRST) POOL_LAUNCH_OP(POOL_FIRST);
+  else if (op == POOL_LAST) POOL_LAUNCH_OP(POOL_LAST);
+  else if (op == POOL_FIRST_LAST) POOL_LAUNCH_OP(POOL_FIRST_LAST);
+  else POOL_LAUNCH_OP(POOL_MEAN);
+#undef POOL_LAUNCH_OP
+#undef POOL_LAUNCH
   KBNER_LAUNCH_RET();
 }
 

@@ -10,8 +10,9 @@ sub-token text (:3347-3408), counts clamped to `maximum_subtoken_length` (:3182-
 Difference by design: nothing numeric happens here.  The reference runs the HF encoder inside this class and bounces
 [B,n,H] features through the CPU; here the class only produces the INTEGER batch (ids, mask, first-sub-token index) and
 the encoder itself lives in the tagger's HIP engine (kbner.engine.Tagger), which keeps hidden states on the device.
-Only the configuration the KB-NER YAMLs use is implemented: layers '-1', pooling_operation 'first', single 512 window
-(inputs are cut to <= 510 sub-tokens at data-generation time, kb/context_process.py:974); anything else raises."""
+The fine-tuning path (fine_tune: true) pools the first sub-token (pooling_operation 'first') of a layer selection; frozen embeddings
+of the stacked tagger (use_rnn: true) take all four pooling operations (:3318-3331) through prepare_pool_batch's span tables and
+kbner_pool_rows_layers.  Anything else raises."""
 import json
 import logging
 import os
@@ -136,6 +137,7 @@ def _load_hf_dir(model_dir):
 
 
 MAX_EMBEDDING_WIDTH = 8192   # the widest token feature the emission head's kernels take (kbner.engine.HEAD_MAX_WIDTH)
+POOLING_OPERATIONS = ("first", "last", "first_last", "mean")   # the reference's four (:3318-3331)
 
 
 class TransformerWordEmbeddings(TokenEmbeddings):
@@ -149,9 +151,12 @@ class TransformerWordEmbeddings(TokenEmbeddings):
         if not os.path.isdir(model):
             raise FileNotFoundError("TransformerWordEmbeddings(model=%r): a local HF directory is required (no network); it must "
                                     "hold the tokenizer files, config.json and model.safetensors / pytorch_model.bin" % model)
-        if pooling_operation != "first":
-            raise NotImplementedError("pooling_operation=%r: only 'first' (the KB-NER configs) is on the MI355X path; the layer "
-                                      "selection (`layers`, `use_scalar_mix`) is" % (pooling_operation,))
+        if pooling_operation not in POOLING_OPERATIONS:
+            raise ValueError("pooling_operation=%r: one of %s" % (pooling_operation, ", ".join(repr(o) for o in POOLING_OPERATIONS)))
+        if pooling_operation != "first" and fine_tune:
+            raise NotImplementedError("pooling_operation=%r: only 'first' (the KB-NER configs) is on the MI355X fine-tuning path; the "
+                                      "layer selection (`layers`, `use_scalar_mix`) is.  Frozen embeddings (fine_tune: false) of the "
+                                      "stacked tagger (use_rnn: true) do take 'last', 'first_last' and 'mean'" % (pooling_operation,))
         if document_extraction or ext_doc or sentence_feat:
             raise NotImplementedError("document_extraction / ext_doc / sentence_feat are outside the hot path (SURVEY.md §8f-3); "
                                       "v2_doc (document windows) is supported")
@@ -182,7 +187,8 @@ class TransformerWordEmbeddings(TokenEmbeddings):
             raise ValueError("layers=%r: a selection names 1 to 32 hidden states" % (layers,))
         self.pooling_operation = pooling_operation
         self.use_scalar_mix = bool(use_scalar_mix)
-        width = int(config.hidden_size) * (1 if self.use_scalar_mix else len(self.layer_indexes))
+        # 'first_last' concatenates the first and the last sub-token: twice the width per layer (the reference's :3889)
+        width = int(config.hidden_size) * (1 if self.use_scalar_mix else len(self.layer_indexes)) * (2 if pooling_operation == "first_last" else 1)
         if width > MAX_EMBEDDING_WIDTH:
             raise NotImplementedError("layers=%r concatenates %d hidden states into a token feature of width %d; the emission head "
                                       "takes at most %d columns -- select fewer layers, or set use_scalar_mix: true (their mean, "
@@ -211,7 +217,8 @@ class TransformerWordEmbeddings(TokenEmbeddings):
 
     @property
     def embedding_length(self) -> int:
-        return self._hidden if self.use_scalar_mix else len(self.layer_indexes) * self._hidden
+        per_layer = self._hidden * (2 if self.pooling_operation == "first_last" else 1)
+        return per_layer if self.use_scalar_mix else len(self.layer_indexes) * per_layer
 
     @property
     def layers(self) -> str:
@@ -283,9 +290,8 @@ class TransformerWordEmbeddings(TokenEmbeddings):
             pass
         return out
 
-    def _tokenize_sentence(self, sentence):
-        """-> (encoder rows [ids incl. <s>/</s>] -- one per sliding window --, window of each word token's first sub-token,
-        its position inside that row (-1 = no sub-token))"""
+    def _sentence_pieces(self, sentence):
+        """-> (content sub-token ids, kept sub-tokens per word token): <EOS> substituted, counts clamped to maximum_subtoken_length"""
         words = [self._eos_text if t.text == "<EOS>" else t.text for t in sentence]
         text = " ".join(words)
         pieces = self.tokenizer.tokenize(text)
@@ -302,7 +308,12 @@ class TransformerWordEmbeddings(TokenEmbeddings):
                 pos += c
             pieces = kept
             counts = [min(c, self.maximum_subtoken_length) for c in counts]
-        ids = list(self.tokenizer.convert_tokens_to_ids(pieces))
+        return list(self.tokenizer.convert_tokens_to_ids(pieces)), counts
+
+    def _tokenize_sentence(self, sentence):
+        """-> (encoder rows [ids incl. <s>/</s>] -- one per sliding window --, window of each word token's first sub-token,
+        its position inside that row (-1 = no sub-token))"""
+        ids, counts = self._sentence_pieces(sentence)
         windows, where = self.split_windows(len(ids))
         first_row, first, g = [], [], 0
         for c in counts:
@@ -316,6 +327,28 @@ class TransformerWordEmbeddings(TokenEmbeddings):
             g += c
         rows = [[self._bos_id] + ids[lo:hi] + [self._eos_id] for lo, hi in windows]
         return rows, first_row, first
+
+    def sentence_spans(self, sentence):
+        """-> (encoder rows as _tokenize_sentence gives them, spans): spans[i] lists the (window, position inside the window's row) of
+        EVERY kept sub-token of word token i, each resolved through split_windows' where(g) on its own -- a word that straddles a
+        sliding-window seam has entries in two windows (the stitched sequence of flair/embeddings.py:3292-3299); a sub-token no window
+        covers (a truncated sentence) has no entry.  Cached per Sentence object like tokenize_sentence."""
+        key = (self.name, self.max_subtokens_sequence_length, self.stride, self.maximum_subtoken_length, len(sentence))
+        cache = getattr(sentence, "_kbner_spans", None)
+        if cache is not None and cache[0] == key:
+            return cache[1]
+        ids, counts = self._sentence_pieces(sentence)
+        windows, where = self.split_windows(len(ids))
+        spans, g = [], 0
+        for c in counts:
+            spans.append([wp for wp in (where(g + i) for i in range(c)) if wp[1] >= 0])
+            g += c
+        out = ([[self._bos_id] + ids[lo:hi] + [self._eos_id] for lo, hi in windows], spans)
+        try:
+            sentence._kbner_spans = (key, out)
+        except AttributeError:
+            pass
+        return out
 
     def split_windows(self, n_ids):
         """Sliding windows over a sentence of n_ids content sub-tokens (flair/embeddings.py:3203-3227: encode_plus with
@@ -455,6 +488,49 @@ class TransformerWordEmbeddings(TokenEmbeddings):
             f2[b, :k] = first[b, :k]
             r2[b, :k] = first_row[b, :k]
         return ids, am, f2, np.asarray([len(s) for s in sentences], np.int64), r2
+
+    def prepare_pool_batch(self, sentences):
+        """prepare_stack_batch's companion for every pooling operation (the frozen-stack path): the same encoder batch -- the same
+        `use_internal_doc` / `doc_sent` handling, maximum_subtoken_length clamp and v2_doc window -- with a SPAN of sub-tokens per word
+        token instead of its first one.  -> (ids, am [R, S0], lengths [B], span_ptr int64 [B * n + 1], span_rows_local int64 [N, 2]):
+        word token t of sentence b is row b * n + t (n = the longest sentence), its kept sub-tokens are the entries
+        span_rows_local[span_ptr[b * n + t]:span_ptr[b * n + t + 1]], each an (encoder row, position inside that row); padding rows and
+        word tokens without a sub-token have empty spans.  Once the padded row length S is known (kbner.batch.assemble) the flat rows
+        of the encoder matrix are span_rows_local[:, 0] * S + span_rows_local[:, 1]."""
+        src = [getattr(s, "doc_sent", s) for s in sentences] if self.use_internal_doc else list(sentences)
+        B, n = len(sentences), max(len(s) for s in sentences)
+        per_sentence = []              # [(first encoder row of the sentence, spans)]
+        if getattr(self, "v2_doc", False):
+            ids, am = self._prepare_batch_v2doc(src)[:2]
+            model_max = min(int(getattr(self.tokenizer, "model_max_length", 512) or 512) - 2, 510)
+            for b, s in enumerate(src):
+                _, pos, counts = self._v2_window(s, model_max)
+                spans = []
+                for c in counts:
+                    spans.append([(0, pos + i) for i in range(c)])
+                    pos += c
+                per_sentence.append((b, spans))
+        else:
+            toks = [self.sentence_spans(s) for s in src]
+            R = sum(len(t[0]) for t in toks)
+            S0 = max(len(r) for t in toks for r in t[0])
+            ids = np.zeros((R, S0), np.int64)
+            am = np.zeros((R, S0), np.int64)
+            r0 = 0
+            for rows, spans in toks:
+                for j, r in enumerate(rows):
+                    ids[r0 + j, :len(r)] = r
+                    am[r0 + j, :len(r)] = 1
+                per_sentence.append((r0, spans))
+                r0 += len(rows)
+        span_ptr = np.zeros(B * n + 1, np.int64)
+        entries = []
+        for b, (s, (r0, spans)) in enumerate(zip(sentences, per_sentence)):
+            for t in range(min(len(s), len(spans))):        # (:3283-3284: zip over the input sentence truncates)
+                entries += [(r0 + w, pos) for w, pos in spans[t]]
+                span_ptr[b * n + t + 1] = len(spans[t])
+        span_ptr = np.cumsum(span_ptr)
+        return ids, am, np.asarray([len(s) for s in sentences], np.int64), span_ptr, np.asarray(entries, np.int64).reshape(-1, 2)
 
     def _add_embeddings_internal(self, sentences):
         """stores the integer batch on the BatchedData (or returns it); the tagger's engine turns it into features"""

@@ -190,6 +190,14 @@ class SequenceTagger(flair.nn.Model):
             if hasattr(embeddings, "embeddings") and len(embeddings.embeddings) != 1:
                 raise NotImplementedError("the fine-tuning path (use_rnn: false) takes exactly one TransformerWordEmbeddings; "
                                           "stacked embeddings go with use_rnn: true (inference)")
+            # the engine of this path pools the FIRST sub-token whatever the embedding says (frozen or not: a frozen teacher too), and
+            # its head is k * H wide: another pooling_operation is refused here, never quietly replaced
+            pooling = getattr(emb, "pooling_operation", "first")
+            if pooling != "first":
+                raise NotImplementedError("use_rnn: false with TransformerWordEmbeddings(%s, pooling_operation=%r): the tagger on the "
+                                          "transformer's own features pools the first sub-token only; 'last', 'first_last' and 'mean' "
+                                          "are taken from frozen embeddings by the stacked tagger (use_rnn: true)"
+                                          % (getattr(emb, "name", type(emb).__name__), pooling))
             for k, p in (("dropout", dropout), ("locked_dropout", locked_dropout)):
                 if not 0.0 <= float(p or 0.0) < 1.0:
                     raise ValueError("%s must be in [0, 1) (got %r)" % (k, p))
@@ -256,11 +264,13 @@ class SequenceTagger(flair.nn.Model):
         embs = list(self.embeddings.embeddings) if hasattr(self.embeddings, "embeddings") else [self.embeddings]
         from flair.embeddings import TransformerWordEmbeddings
         for e in embs:
-            if isinstance(e, TransformerWordEmbeddings) and (e.use_scalar_mix or list(e.layer_indexes) not in (
-                    [-1], [int(e.model.config.num_hidden_layers)])):
-                raise NotImplementedError("use_rnn: true with TransformerWordEmbeddings(%s, layers=%r%s): the inference stack keeps its "
-                                          "input layout, one last-layer block per encoder (layers='-1'); the layer selection is "
-                                          "implemented for the fine-tuning tagger (use_rnn: false)"
+            # a FROZEN TransformerWordEmbeddings brings any layer selection, use_scalar_mix and the four pooling operations (one
+            # kbner_pool_rows_layers launch into its block, embedding_length wide); one with fine_tune: true is refused as before
+            if isinstance(e, TransformerWordEmbeddings) and getattr(e, "fine_tune", False) and (e.use_scalar_mix or list(
+                    e.layer_indexes) not in ([-1], [int(e.model.config.num_hidden_layers)])):
+                raise NotImplementedError("use_rnn: true with TransformerWordEmbeddings(%s, layers=%r%s, fine_tune=True): the stack takes a "
+                                          "layer selection from FROZEN embeddings only (fine_tune: false); the layer selection with "
+                                          "gradients is implemented for the fine-tuning tagger (use_rnn: false)"
                                           % (e.name, e.layers, ", use_scalar_mix=True" if e.use_scalar_mix else ""))
         self._stack_embs = sorted(embs, key=lambda e: e.name)
         blocks = [int(e.embedding_length) for e in self._stack_embs]
@@ -283,11 +293,17 @@ class SequenceTagger(flair.nn.Model):
     def load_stack_state(self, state):
         """state: {"rnn": torch.nn.LSTM state dict, "linear.weight" [T, 2H], "linear.bias" [T], "transitions" [T, T]}"""
         from kbner import stack as K
-        self._stack_state = {"rnn": {k: torch.as_tensor(v).detach().float().cpu() for k, v in state["rnn"].items()},
-                             "linear.weight": torch.as_tensor(state["linear.weight"]).detach().float().cpu(),
-                             "linear.bias": torch.as_tensor(state["linear.bias"]).detach().float().cpu(),
-                             "transitions": torch.as_tensor(state["transitions"]).detach().float().cpu()}
-        st = self.__dict__["_stack_state_host"]
+        st = {"rnn": {k: torch.as_tensor(v).detach().float().cpu() for k, v in state["rnn"].items()},
+              "linear.weight": torch.as_tensor(state["linear.weight"]).detach().float().cpu(),
+              "linear.bias": torch.as_tensor(state["linear.bias"]).detach().float().cpu(),
+              "transitions": torch.as_tensor(state["transitions"]).detach().float().cpu()}
+        D, got = sum(self._stack_blocks), int(st["rnn"]["weight_ih_l0"].shape[1])
+        if got != D:       # (refused before anything is replaced: deep inside the head it would be a shape error without a name)
+            raise ValueError("load_stack_state: weight_ih_l0 reads %d input columns but this stack's embeddings are %d wide (blocks %s): "
+                             "the state belongs to another embedding list, or to a pooling_operation / layers / use_scalar_mix setting "
+                             "of another width.  (Only the width is checked: the state records neither pooling nor layers, so a "
+                             "setting of the SAME width loads)" % (got, D, self._stack_blocks))
+        self._stack_state = st
         head = getattr(self, "stack_head", None)
         if head is not None and head.arena is not None:
             # a trainable tagger: the arena is refreshed in place and the optimizer moments of the old weights are dropped
@@ -436,6 +452,12 @@ class SequenceTagger(flair.nn.Model):
         head = self.stack_head
         return FeatureStore.launch(src, head.rows(B, n), head.Dp), lengths, B, n
 
+    @staticmethod
+    def _plain_first(emb):
+        """first sub-token of the last layer alone: the producer the stack has always had (encoder_forward + kbner_gather_rows_ld)"""
+        return (emb.pooling_operation == "first" and not emb.use_scalar_mix
+                and list(emb.layer_indexes) in ([-1], [int(emb.model.config.num_hidden_layers)]))
+
     def _stack_compute(self, sentences):
         """X filled in place by the selected embeddings' device producers; added to an open feature store"""
         from kbner import batch as kb
@@ -454,7 +476,19 @@ class SequenceTagger(flair.nn.Model):
             if sel is not None and float(sel[slot]) != 1.0:
                 raise NotImplementedError("fractional embedding selection weights are not supported (best_action is 0/1)")
             col = head.cols[slot]
-            if isinstance(emb, TransformerWordEmbeddings):
+            if isinstance(emb, TransformerWordEmbeddings) and not self._plain_first(emb):
+                # any pooling operation / layer selection: the encoder once, then ONE segmented reduction over the selected hidden
+                # states into the block (kbner_pool_rows_layers; flair/embeddings.py:3303-3345)
+                ids, am, lens, span_ptr, span_loc = emb.prepare_pool_batch(sentences)
+                none = np.full((B, n), -1, np.int64)
+                hb = kb.assemble(ids, am, none, np.zeros((B, n), np.int64), lens, None)
+                db = kb.to_device(hb, flair.device)
+                enc = self._encoder_for(emb)
+                enc.encoder_forward(db["ids"], db["pos_ids"], db["maskbias"], db["R"], db["S"], need_grad=False)
+                states = enc.acts(db["R"], db["S"]).x      # hidden_states[0..L] (0 = embedding output)
+                ops.pool_rows_layers([states[li] for li in emb.layer_indexes], span_ptr, span_loc[:, 0] * db["S"] + span_loc[:, 1], X,
+                                     col, emb.pooling_operation, layer_mean=emb.use_scalar_mix)
+            elif isinstance(emb, TransformerWordEmbeddings):
                 ids, am, first, lens, first_row = emb.prepare_stack_batch(sentences)
                 hb = kb.assemble(ids, am, first, np.zeros(first.shape, np.int64), lens, None, first_row=first_row)
                 db = kb.to_device(hb, flair.device)

@@ -44,6 +44,7 @@ SIGNATURES = {
     "kbner_scatter_rows_drop": (c_int, [P, P, P, c_int, c_int, c_int, U32, U32, U32, U32, P]),
     "kbner_gather_rows_layers": (c_int, [P, c_int, c_int, P, P, c_int, c_int, c_int, U32, U32, U32, U32, P]),
     "kbner_scatter_add_rows_ld": (c_int, [P, c_int, c_int, P, P, c_int, c_int, c_float, c_int, U32, U32, U32, U32, P]),
+    "kbner_pool_rows_layers": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P]),
     "kbner_gather_rows_ld": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P]),
     "kbner_gather_rows_blocks_drop": (c_int, [P, c_int, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, U32, U32, U32, U32, P]),
     "kbner_gather_rows_f32": (c_int, [P, P, P, c_int, c_int, P]),

@@ -390,6 +390,77 @@ def gather_rows_layers(srcs, idx, n, mean=False, drop_e=NO_DROP, drop_l=NO_DROP,
     return out
 
 
+POOL_OPS = {"first": 0, "last": 1, "first_last": 2, "mean": 3}     # kbner_pool_rows_layers' op codes
+
+
+def pool_width(op, k, H, layer_mean=False):
+    """columns kbner_pool_rows_layers writes: k (1 under the layer mean) pooled values of H (first_last: 2 H) columns"""
+    return (2 if POOL_OPS[op] == 2 else 1) * int(H) * (1 if layer_mean else int(k))
+
+
+def check_pool_tables(span_ptr, span_rows, src_rows):
+    """The table contract of kbner_pool_rows_layers, which the library cannot check (the tables live in device memory): span_ptr
+    [R + 1] non-decreasing from 0 and ending at len(span_rows); every entry of span_rows a row of the sources (0 <= row < src_rows).
+    -> (span_ptr, span_rows) as contiguous int32 host tensors"""
+    tabs = []
+    for name, t in (("span_ptr", span_ptr), ("span_rows", span_rows)):
+        t = torch.as_tensor(t)
+        if t.is_cuda or t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+            raise L.KbnerError("pool_rows_layers: %s is a HOST 1-d integer array (int32 / int64)" % name)
+        tabs.append(t.to(torch.int64))
+    sp, sr = tabs
+    if sp.numel() < 1 or int(sp[0]) != 0 or bool((sp[1:] < sp[:-1]).any()):
+        raise L.KbnerError("pool_rows_layers: span_ptr must be non-decreasing and start at 0")
+    if int(sp[-1]) != sr.numel():
+        raise L.KbnerError("pool_rows_layers: span_ptr ends at %d but span_rows holds %d entries" % (int(sp[-1]), sr.numel()))
+    if sr.numel() and (int(sr.min()) < 0 or int(sr.max()) >= int(src_rows)):
+        raise L.KbnerError("pool_rows_layers: span_rows must lie in [0, %d), the rows of the sources (got %d .. %d)"
+                           % (int(src_rows), int(sr.min()), int(sr.max())))
+    return sp.to(I32).contiguous(), sr.to(I32).contiguous()
+
+
+def pool_rows_layers(srcs, span_ptr, span_rows, out2d, col, op, layer_mean=False):
+    """Sub-token pooling over a layer selection, written into a column block (include/kbner.h kbner_pool_rows_layers):
+    out2d[r, col:col + W] = the pooled feature of word r, whose sub-tokens are the rows span_rows[span_ptr[r]:span_ptr[r + 1]] of the
+    k bf16 [*, H] hidden states srcs (an empty span gives zeros).  op: 'first' / 'last' / 'first_last' / 'mean'; layer_mean: the mean of
+    the k pooled values instead of their concatenation; W = pool_width(op, k, H, layer_mean).  span_ptr [R + 1], span_rows: HOST integer
+    arrays, checked here (check_pool_tables) and then uploaded -- a bad table raises, it never reaches the device.  Rows >= R and columns
+    outside the block are not touched."""
+    srcs = list(srcs)
+    k = len(srcs)
+    if op not in POOL_OPS:
+        raise L.KbnerError("pool_rows_layers: op must be one of %s (got %r)" % (", ".join(POOL_OPS), op))
+    if not 1 <= k <= 32:
+        raise L.KbnerError("pool_rows_layers: 1 to 32 source matrices (got %d)" % k)
+    for t, name in [(s_, "srcs[%d]" % i) for i, s_ in enumerate(srcs)] + [(out2d, "out2d")]:
+        if not torch.is_tensor(t) or t.dtype != BF16 or t.dim() != 2 or not t.is_contiguous():
+            raise L.KbnerError("pool_rows_layers: %s must be a contiguous 2-d bfloat16 tensor" % name)
+    H = srcs[0].shape[1]
+    if any(s_.shape[1] != H for s_ in srcs) or H % 8 or H == 0:
+        raise L.KbnerError("pool_rows_layers: every source is bf16 [*, H] with one H %% 8 == 0 (got %s)" % [tuple(s_.shape) for s_ in srcs])
+    sp, sr = check_pool_tables(span_ptr, span_rows, min(s_.shape[0] for s_ in srcs))
+    R, W, col, ld = sp.numel() - 1, pool_width(op, k, H, layer_mean), int(col), out2d.shape[1]
+    if R > out2d.shape[0]:
+        raise L.KbnerError("pool_rows_layers: %d spans but out2d holds %d rows" % (R, out2d.shape[0]))
+    if col < 0 or col % 8 or ld % 8 or col + W > ld:
+        raise L.KbnerError("pool_rows_layers: the block [col, col + W) = [%d, %d) must start at a multiple of 8 and lie inside the %d "
+                           "columns of out2d (a multiple of 8)" % (col, col + W, ld))
+    for t, name in [(s_, "srcs[%d]" % i) for i, s_ in enumerate(srcs)] + [(out2d, "out2d")]:
+        if not t.is_cuda or t.device != out2d.device:
+            raise L.KbnerError("pool_rows_layers: %s must be a cuda tensor on out2d's device" % name)
+    if (out2d.data_ptr() + 2 * col) % 16:
+        raise L.KbnerError("pool_rows_layers: the block must start on a 16-byte boundary")
+    if R == 0:
+        return out2d
+    if sr.numel() == 0:      # every span empty: the kernel reads no entry, but takes no null table
+        sr = torch.zeros(1, dtype=I32)
+    sp, sr = sp.to(out2d.device), sr.to(out2d.device)
+    ptrs = (ctypes.c_void_p * k)(*[s_.data_ptr() for s_ in srcs])
+    L.call("kbner_pool_rows_layers", ptrs, k, 1 if layer_mean else 0, POOL_OPS[op], ptr(sp), ptr(sr),
+           c_void_p(out2d.data_ptr() + 2 * col), ld, R, H, stream_ptr())
+    return out2d
+
+
 def scatter_add_rows_ld(dout, col0, idx, dst, n, scale=1.0, drop_e=NO_DROP, drop_l=NO_DROP):
     """its backward for one source: dst[idx[r], :] += dout[r, col0:col0 + H] * m[r, col0:col0 + H] * scale for idx[r] >= 0 (unique
     indices; other rows untouched).  dout bf16 [R, ld], dst bf16 [*, H]; the masks are keyed by the column of the ld-wide row."""
