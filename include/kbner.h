@@ -451,6 +451,37 @@ int kbner_lstm_seq_bwd(const kbner_bf16* dout, int ldo, const int* out_col, cons
                        const kbner_bf16* gates, const float* cs, float* dc_carry, kbner_bf16* dgx, int ld_dgx, int steps, int B,
                        int Hp, int ndir, void* stream);
 
+/* ---------------- character BiLSTM of FastCharacterEmbeddings (csrc/char_lstm.hip) ---------------- */
+/* flair/embeddings.py:670-758: torch.nn.Embedding -> one-layer bidirectional torch.nn.LSTM over every word's characters
+ * (pack_padded_sequence, enforce_sorted=False, zero initial state) -> hidden[0]; trained by autograd in the reference.  Here the whole
+ * recurrence is ONE launch forward and ONE launch backward (one wave per word, both directions in its two halves, weights in LDS).
+ *   emb f32 [V, E]; wih f32 [2, 4Hc, E]; whh f32 [2, 4Hc, Hc]; bias_ih, bias_hh f32 [2, 4Hc]: torch's layouts, gate order i|f|g|o
+ *   chars i32 [W, Lmax] (ids in [0, V)); lens i32 [W] (1 <= len <= Lmax); rows i32 [W]: the row of the output matrix word w owns,
+ *   unique, or -1 for a word WordDropout removed (nothing written, nothing saved, no gradient).  The tables live in device memory: the
+ *   caller checks them (kbner.ops.check_char_tables).
+ * kbner_char_lstm_fwd: out bf16, row stride ld_out, pointing at the block's first column, which is column col0 of the ld_out-wide row:
+ *   out[rows[w], 0:Hc]   = the forward direction's h after lens[w] steps
+ *   out[rows[w], Hc:2Hc] = the backward direction's h after reading characters lens[w] - 1 .. 0
+ * fp32 arithmetic, one rounding to bf16; then the two pre-RNN dropout sites of kbner_gather_rows_drop multiply the rounded value, keyed
+ * as that kernel keys element (row, col0 + c) of the ld_out-wide matrix (element site: (row, column); locked site: (row / n, column);
+ * threshold 0 disables a site), so the write equals kbner_gather_rows_drop over the unmasked write bit for bit.  Only columns
+ * [0, 2Hc) of the named rows are written.  ws: kbner_char_lstm_ws_bytes(W, Lmax, Hc) bytes that receive what the backward reads, or
+ * NULL (forward only).  1 <= E, Hc <= 32, ld_out % 8 == 0, col0 % 8 == 0, col0 + 2Hc <= ld_out, out 16-byte aligned, n >= 1; W == 0
+ * launches nothing.
+ * kbner_char_lstm_bwd: dout bf16, row stride ld_out, pointing at the first column of d loss / d the masked block, row for row as the
+ * forward's matrix; it may be a narrower matrix than the forward's (ld_out >= 2Hc): col0 is the forward's col0, read for the mask keys only.  Back-propagation through time per word
+ * and direction from dh_final = dout (.) mask; ADDS the gradients to d_emb f32 [V, E] (scatter-add over character ids), d_wih, d_whh,
+ * d_bias_ih and d_bias_hh (the two receive the same sums).  fp32 atomics: the summation order varies between runs. */
+size_t kbner_char_lstm_ws_bytes(int W, int Lmax, int Hc);
+int kbner_char_lstm_fwd(const float* emb, const float* wih, const float* whh, const float* bias_ih, const float* bias_hh,
+                        const int* chars, const int* lens, const int* rows, kbner_bf16* out, int ld_out, int col0, float* ws, int W,
+                        int Lmax, int V, int E, int Hc, int n, uint32_t seed_e, uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l,
+                        void* stream);
+int kbner_char_lstm_bwd(const kbner_bf16* dout, int ld_out, int col0, const float* emb, const float* wih, const float* whh,
+                        const int* chars, const int* lens, const int* rows, const float* ws, float* d_emb, float* d_wih, float* d_whh,
+                        float* d_bias_ih, float* d_bias_hh, int W, int Lmax, int V, int E, int Hc, int n, uint32_t seed_e,
+                        uint32_t thresh_e, uint32_t seed_l, uint32_t thresh_l, void* stream);
+
 /* ---------------- optimiser (transformers==3.0.0 AdamW + clip_grad_norm_, finetune_trainer.py:1010,1018) ------------- */
 int kbner_sqnorm_ws_floats(void);
 int kbner_grad_sqnorm(const float* g, size_t n, float* ws, float* out, int accumulate, void* stream);

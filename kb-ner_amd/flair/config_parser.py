@@ -71,14 +71,36 @@ class ConfigParser:
             parts["test"].append(ds.test)
         return ListCorpus(**parts, targets=names)
 
+    def train_full_tokenset(self):
+        """[train tokens, tokens of train + dev + test], each by falling frequency and cut at `train.min_freq`: what the reference
+        keeps as self.tokens (config_parser.py:71 -> Corpus.get_train_full_tokenset, flair/data.py:901-923).  Built on first use."""
+        if self.tokens is None:
+            from collections import Counter
+            min_freq = self.config["train"].get("min_freq", -1)
+
+            def common(sentences):
+                out = []
+                for token, freq in Counter(t.text for s in sentences for t in s.tokens).most_common():
+                    if min_freq != -1 and freq < min_freq:
+                        break
+                    out.append(token)
+                return out
+            train = self.corpus.train
+            self.tokens = [common(train[i] for i in range(len(train))), common(self.corpus.get_all_sentences())]
+        return self.tokens
+
     def create_embeddings(self, embeddings: dict):
-        built = []
+        built, char_map = [], None
         for key, kw in embeddings.items():
             cls = getattr(Embeddings, key.split("-")[0], None)
             if cls is None:
                 raise NotImplementedError("embedding class %s is outside the hot path" % key.split("-")[0])
-            built.append(cls(**kw) if isinstance(kw, dict) else cls())
-        return Embeddings.StackedEmbeddings(embeddings=built), None, None, None, None
+            if "FastCharacterEmbeddings" in key:      # (config_parser.py:164-173: with and without a kwargs dict)
+                built.append(cls(vocab=self.train_full_tokenset()[1], **(kw if isinstance(kw, dict) else {})))
+                char_map = built[-1].char_dictionary
+            else:
+                built.append(cls(**kw) if isinstance(kw, dict) else cls())
+        return Embeddings.StackedEmbeddings(embeddings=built), None, char_map, None, None
 
     def create_model(self, config=None, pretrained=False, is_student=False, crf=True):
         config = self.config if config is None else config

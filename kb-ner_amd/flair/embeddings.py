@@ -702,6 +702,82 @@ class FlairEmbeddings(TokenEmbeddings):
         return self.name
 
 
+class FastCharacterEmbeddings(TokenEmbeddings):
+    """Character embeddings of words (Lample et al., 2016), the one TRAINED candidate of the ACE embedding lists: a character
+    lookup table and a one-layer bidirectional LSTM over each word's characters; the word's feature is the forward direction's
+    state after its last character beside the backward direction's state after its first.
+
+    Behavioural reference (restated): flair/embeddings.py FastCharacterEmbeddings (:670-758).  char_dictionary as :692-699 ('<u>' is 0,
+    then the characters of `vocab` in first-seen order, then ' ' and '\\n'); name 'Char'; static_embeddings False; embedding_length
+    2 * char_embedding_dim (:719) -- the block really is 2 * hidden_size_char wide, so hidden_size_char != char_embedding_dim (where the
+    reference's tagger fails on the width) is refused here; torch's default initialisation of torch.nn.Embedding and torch.nn.LSTM,
+    drawn on the host (the reference's _init_embeddings, :722-723, is never called and names a module that file does not import).
+    char_cnn is not implemented.  Only the bookkeeping is host code: the modules held here are the INITIAL values and the names of the
+    state dict; the stacked tagger copies them into a device arena (kbner.stack.CharBiLSTM) and runs and trains them there through
+    kbner_char_lstm_fwd / kbner_char_lstm_bwd."""
+    MAX_DIM = 32      # kbner_char_lstm_fwd: one lane per hidden unit / embedding column in half a wave
+
+    def __init__(self, vocab=None, char_embedding_dim: int = 25, hidden_size_char: int = 25, char_cnn=False, debug=False,
+                 embedding_name: str = None):
+        super().__init__()
+        if char_cnn:
+            raise NotImplementedError("FastCharacterEmbeddings(char_cnn=True): the character CNN is outside the hot path; the character "
+                                      "BiLSTM (char_cnn: false) is implemented")
+        if int(hidden_size_char) != int(char_embedding_dim):
+            raise ValueError("FastCharacterEmbeddings(char_embedding_dim=%d, hidden_size_char=%d): embedding_length is 2 * "
+                             "char_embedding_dim but the features are 2 * hidden_size_char wide; the two must be equal"
+                             % (char_embedding_dim, hidden_size_char))
+        if not 1 <= int(char_embedding_dim) <= self.MAX_DIM:
+            raise ValueError("FastCharacterEmbeddings: char_embedding_dim = hidden_size_char = %d is outside [1, %d], the sizes the "
+                             "character kernels take" % (char_embedding_dim, self.MAX_DIM))
+        if vocab is None:
+            raise ValueError("FastCharacterEmbeddings needs `vocab`, the corpus's token set its character dictionary is built from "
+                             "(ConfigParser.create_embeddings passes it)")
+        self.name = "Char" if embedding_name is None else embedding_name
+        self.static_embeddings = False
+        self.char_cnn = False
+        self.debug = debug
+        self.char_dictionary = {"<u>": 0}
+        for word in vocab:
+            for c in word:
+                if c not in self.char_dictionary:
+                    self.char_dictionary[c] = len(self.char_dictionary)
+        self.char_dictionary[" "] = len(self.char_dictionary)
+        self.char_dictionary["\n"] = len(self.char_dictionary)
+        self.char_embedding_dim, self.hidden_size_char = int(char_embedding_dim), int(hidden_size_char)
+        self.char_embedding = torch.nn.Embedding(len(self.char_dictionary), self.char_embedding_dim)
+        self.char_layer = torch.nn.LSTM(self.char_embedding_dim, self.hidden_size_char, num_layers=1, bidirectional=True)
+        self._length = 2 * self.char_embedding_dim
+
+    @property
+    def embedding_length(self) -> int:
+        return self._length
+
+    def char_batch(self, sentences, n):
+        """-> (chars int32 [W, Lmax], lens int32 [W], rows int32 [W]): one entry per real word of the batch -- its character ids
+        ('<u>' for a character outside the dictionary, and as padding: custom_data_loader._get_char_idx :418-433), its length, and its
+        token-major feature row b * n + token.  Padding positions get no entry: their rows stay zero."""
+        words = [(b * int(n) + k, tok.text) for b, s in enumerate(sentences) for k, tok in enumerate(s.tokens)]
+        if any(len(t) == 0 for _, t in words):
+            raise ValueError("FastCharacterEmbeddings.char_batch: a token with empty text has no characters to read")
+        W = len(words)
+        Lmax = max([len(t) for _, t in words], default=1)
+        unk = self.char_dictionary["<u>"]
+        chars = np.full((W, Lmax), unk, np.int32)
+        lens = np.zeros(W, np.int32)
+        rows = np.zeros(W, np.int32)
+        for w, (r, t) in enumerate(words):
+            chars[w, :len(t)] = [self.char_dictionary.get(c, unk) for c in t]
+            lens[w], rows[w] = len(t), r
+        return chars, lens, rows
+
+    def _add_embeddings_internal(self, sentences):
+        return sentences   # the block is produced on the device by the tagger's stack (kbner.stack.CharStep)
+
+    def __str__(self):
+        return self.name
+
+
 class _NeedsExternalWeights(TokenEmbeddings):
     """Embedding classes of the ACE config (config/xlmr-task-wiki-extdoc...ner6.yaml) whose weights are files this offline
     build cannot obtain ("ELMo/FastWord need external weight files and can stay stubbed").  They are

@@ -274,6 +274,14 @@ class SequenceTagger(flair.nn.Model):
                                           % (e.name, e.layers, ", use_scalar_mix=True" if e.use_scalar_mix else ""))
         self._stack_embs = sorted(embs, key=lambda e: e.name)
         blocks = [int(e.embedding_length) for e in self._stack_embs]
+        # the one trained candidate: FastCharacterEmbeddings (a 50-wide block in sorted-name order like every other; its parameters
+        # live in a device arena of their own, kbner.stack.CharBiLSTM)
+        from flair.embeddings import FastCharacterEmbeddings
+        chars = [slot for slot, e in enumerate(self._stack_embs) if isinstance(e, FastCharacterEmbeddings)]
+        if len(chars) > 1:
+            raise NotImplementedError("the stacked tagger takes at most one FastCharacterEmbeddings (got %d)" % len(chars))
+        self._char_slot = chars[0] if chars else None
+        self._char_net_obj = None
         H, D, T = int(self.hidden_size), sum(blocks), self.tagset_size
         g = torch.Generator().manual_seed(int(torch.initial_seed() % (2 ** 31)))
         k = 1.0 / (H ** 0.5)
@@ -287,12 +295,47 @@ class SequenceTagger(flair.nn.Model):
         tr[self.start_idx, :] = -1e12
         tr[:, self.stop_idx] = -1e12
         self._stack_blocks = blocks
-        self.load_stack_state({"rnn": rnn, "linear.weight": u(T, 2 * H, b=kl), "linear.bias": u(T, b=kl), "transitions": tr})
+        self.load_stack_state({"rnn": rnn, "linear.weight": u(T, 2 * H, b=kl), "linear.bias": u(T, b=kl), "transitions": tr}, _init=True)
         self._encoders = {}
 
-    def load_stack_state(self, state):
-        """state: {"rnn": torch.nn.LSTM state dict, "linear.weight" [T, 2H], "linear.bias" [T], "transitions" [T, T]}"""
+    def _char_net(self):
+        """the character BiLSTM's device parameters (None without a FastCharacterEmbeddings), created from the embedding's host
+        modules on first use"""
+        if self.__dict__.get("_char_slot") is None:
+            return None
+        if self._char_net_obj is None:
+            from kbner.stack import CharBiLSTM
+            emb = self._stack_embs[self._char_slot]
+            self._char_net_obj = CharBiLSTM({k: v for k, v in emb.state_dict().items()}, flair.device)
+        return self._char_net_obj
+
+    def _char_step(self, sentences, n):
+        """this batch's kbner.stack.CharStep, or None: no character embedding, or deselected (then neither kernel is launched, the
+        block stays zero and the parameters receive no gradient)"""
+        slot = self.__dict__.get("_char_slot")
+        if slot is None:
+            return None
+        sel = self._stack_selection()
+        if sel is not None and float(sel[slot]) == 0.0:
+            return None
+        if sel is not None and float(sel[slot]) != 1.0:
+            raise NotImplementedError("fractional embedding selection weights are not supported (best_action is 0/1)")
+        from kbner.stack import CharStep
+        chars, lens, rows = self._stack_embs[slot].char_batch(sentences, n)
+        return CharStep(self._char_net(), chars, lens, rows, self.stack_head.cols[slot])
+
+    def load_stack_state(self, state, _init=False):
+        """state: {"rnn": torch.nn.LSTM state dict, "linear.weight" [T, 2H], "linear.bias" [T], "transitions" [T, T]} and, of a tagger
+        with a FastCharacterEmbeddings, {"char": its state dict, "char_dictionary"}"""
         from kbner import stack as K
+        if not _init:
+            has = self.__dict__.get("_char_slot") is not None
+            if has and ("char" not in state or "char_dictionary" not in state):
+                raise ValueError("load_stack_state: this tagger has a FastCharacterEmbeddings but the state carries no character "
+                                 "parameters ('char', 'char_dictionary'): it was saved by a stack without that embedding")
+            if not has and ("char" in state or "char_dictionary" in state):
+                raise ValueError("load_stack_state: the state carries character parameters ('char', 'char_dictionary') but this "
+                                 "tagger's embedding list has no FastCharacterEmbeddings")
         st = {"rnn": {k: torch.as_tensor(v).detach().float().cpu() for k, v in state["rnn"].items()},
               "linear.weight": torch.as_tensor(state["linear.weight"]).detach().float().cpu(),
               "linear.bias": torch.as_tensor(state["linear.bias"]).detach().float().cpu(),
@@ -304,6 +347,18 @@ class SequenceTagger(flair.nn.Model):
                              "of another width.  (Only the width is checked: the state records neither pooling nor layers, so a "
                              "setting of the SAME width loads)" % (got, D, self._stack_blocks))
         self._stack_state = st
+        if not _init and self.__dict__.get("_char_slot") is not None:
+            emb = self._stack_embs[self._char_slot]
+            if len(state["char_dictionary"]) != int(torch.as_tensor(state["char"]["char_embedding.weight"]).shape[0]):
+                raise ValueError("load_stack_state: char_dictionary and char_embedding.weight disagree on the number of characters")
+            if self._char_net_obj is not None and self._char_net_obj.V == len(state["char_dictionary"]):
+                self._char_net_obj.load_state(state["char"])
+            else:
+                from kbner.stack import CharBiLSTM
+                self._char_net_obj = CharBiLSTM(state["char"], flair.device)
+                if getattr(self, "stack_head", None) is not None and getattr(self.stack_head, "char", None) is not None:
+                    self.stack_head.char = self._char_net_obj
+            emb.char_dictionary = dict(state["char_dictionary"])
         head = getattr(self, "stack_head", None)
         if head is not None and head.arena is not None:
             # a trainable tagger: the arena is refreshed in place and the optimizer moments of the old weights are dropped
@@ -319,9 +374,12 @@ class SequenceTagger(flair.nn.Model):
     def _stack_state(self):
         """the stack's weights in the reference's layout; of a trainable tagger: read from the parameter arena"""
         head = getattr(self, "stack_head", None)
-        if head is not None and head.arena is not None:
-            return head.state()
-        return self.__dict__["_stack_state_host"]
+        st = head.state() if (head is not None and head.arena is not None) else self.__dict__["_stack_state_host"]
+        if self.__dict__.get("_char_slot") is not None and "_stack_embs" in self.__dict__:
+            st = dict(st)
+            st["char"] = self._char_net().state()
+            st["char_dictionary"] = dict(self._stack_embs[self._char_slot].char_dictionary)
+        return st
 
     @_stack_state.setter
     def _stack_state(self, st):
@@ -345,6 +403,7 @@ class SequenceTagger(flair.nn.Model):
         head.word_dropout = float(self.use_word_dropout or 0.0)
         head.seed_dropout(int(torch.initial_seed() % (2 ** 31)))
         head.train(self.training)
+        head.char = self._char_net()      # (None without a FastCharacterEmbeddings) what StackOptimizer steps beside the head
         return head
 
     def _encoder_for(self, emb):
@@ -436,7 +495,10 @@ class SequenceTagger(flair.nn.Model):
         if store is None:
             return None
         sel = self._stack_selection()
-        store.select([True] * store.nblk if sel is None else [float(sel[slot]) != 0.0 for slot in range(store.nblk)])
+        on = [True] * store.nblk if sel is None else [float(sel[slot]) != 0.0 for slot in range(store.nblk)]
+        if self.__dict__.get("_char_slot") is not None:
+            on[self._char_slot] = False       # the character block is never stored: its rows change with every step
+        store.select(on)
         return store.source(sentences, n)
 
     def _stack_input(self, sentences):
@@ -447,10 +509,12 @@ class SequenceTagger(flair.nn.Model):
         lengths = np.asarray([len(s) for s in sentences], np.int64)
         B, n = len(sentences), int(lengths.max())
         src = self._stack_source(sentences, n)
-        if src is None:
-            return self._stack_compute(sentences)
         head = self.stack_head
-        return FeatureStore.launch(src, head.rows(B, n), head.Dp), lengths, B, n
+        X = self._stack_compute(sentences)[0] if src is None else FeatureStore.launch(src, head.rows(B, n), head.Dp)
+        char = self._char_step(sentences, n)
+        if char is not None:     # a forward-only pass: the block goes into X itself, both thresholds 0
+            char.forward(X, None, n, save=False)
+        return X, lengths, B, n
 
     @staticmethod
     def _plain_first(emb):
@@ -507,6 +571,8 @@ class SequenceTagger(flair.nn.Model):
                     ops.gather_rows_into(states[len(states) + li], db["row_idx"], X, col + j * Hh, Hh)
             elif isinstance(emb, FlairEmbeddings):
                 char_lms.append((emb, col))     # run together below: one launch per character step for all LMs of a width
+            elif slot == self.__dict__.get("_char_slot"):
+                continue     # trained, never in X or the store: written into the matrix the input GEMM reads (_char_step)
             else:
                 raise NotImplementedError("embedding class %s has no device producer" % type(emb).__name__)
         if char_lms:
@@ -563,6 +629,11 @@ class SequenceTagger(flair.nn.Model):
             yield "linear.bias", self._stack_state["linear.bias"]
             for k, v in self._stack_state["rnn"].items():
                 yield "rnn." + k, v
+            if self.__dict__.get("_char_slot") is not None:     # (names containing 'embedding': the plain learning-rate group)
+                embs = list(self.embeddings.embeddings) if hasattr(self.embeddings, "embeddings") else [self.embeddings]
+                idx = embs.index(self._stack_embs[self._char_slot])
+                for k, v in self._char_net().state().items():
+                    yield "embeddings.list_embedding_%d.%s" % (idx, k), v
             return
         if self.use_crf:   # (the reference creates `transitions` only with use_crf, :390: a softmax student has no such parameter)
             yield "transitions", self.engine.arena.param("transitions")
@@ -578,6 +649,8 @@ class SequenceTagger(flair.nn.Model):
     def zero_grad(self, set_to_none=False):
         if getattr(self, "stack_head", None) is not None and self.stack_head.arena is not None:
             self.stack_head.g.zero_()
+            if getattr(self.stack_head, "char", None) is not None:
+                self.stack_head.char.g.zero_()
         if self.engine is not None and self.engine.arena.g is not None:    # None: a teacher after drop_gradients()
             self.engine.arena.g.zero_()
             self.engine.arena.wgrad_stale = False
@@ -719,8 +792,13 @@ class SequenceTagger(flair.nn.Model):
         db = kb.to_device(hb, flair.device)
         self._last = (hb, db)
         self.mask = db["keep_f"]
-        loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale, weights=sentence_weights,
-                                  source=src)
+        char = self._char_step(data_points, n)
+        if char is None:
+            loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale,
+                                      weights=sentence_weights, source=src)
+        else:
+            loss = head.loss_backward(X, lengths, B, n, db, self.start_idx, self.stop_idx, loss_scale=loss_scale,
+                                      weights=sentence_weights, source=src, char=char)
         self.last_loss_parts = (loss, None)
         return loss
 

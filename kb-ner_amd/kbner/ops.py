@@ -461,6 +461,125 @@ def pool_rows_layers(srcs, span_ptr, span_rows, out2d, col, op, layer_mean=False
     return out2d
 
 
+# ---------------------------------------------------------------- character BiLSTM (csrc/char_lstm.hip)
+CHAR_MAXD = 32          # E and Hc limit of kbner_char_lstm_fwd / _bwd
+
+
+def check_char_tables(chars, lens, rows, V, n_rows):
+    """The table contract of kbner_char_lstm_fwd / _bwd, which the library cannot check (the tables live in device memory): chars
+    [W, Lmax] with every id in [0, V), lens [W] in [1, Lmax], rows [W] each -1 (a dropped word) or a row of the output matrix
+    (0 <= row < n_rows), no row named twice.  HOST integer arrays -> contiguous int32 host tensors"""
+    tabs = []
+    for name, t, dim in (("chars", chars, 2), ("lens", lens, 1), ("rows", rows, 1)):
+        t = torch.as_tensor(t)
+        if t.is_cuda or t.dim() != dim or t.dtype not in (torch.int32, torch.int64):
+            raise L.KbnerError("char_lstm: %s is a HOST %d-d integer array (int32 / int64)" % (name, dim))
+        tabs.append(t.to(torch.int64))
+    ch, ln, rw = tabs
+    W, Lmax = ch.shape
+    if ln.numel() != W or rw.numel() != W or (W and Lmax < 1):
+        raise L.KbnerError("char_lstm: chars [W, Lmax >= 1], lens [W], rows [W] (got %s, %s, %s)"
+                           % (tuple(ch.shape), tuple(ln.shape), tuple(rw.shape)))
+    if W:
+        if int(ch.min()) < 0 or int(ch.max()) >= int(V):
+            raise L.KbnerError("char_lstm: character ids must lie in [0, %d) (got %d .. %d)" % (int(V), int(ch.min()), int(ch.max())))
+        if int(ln.min()) < 1 or int(ln.max()) > Lmax:
+            raise L.KbnerError("char_lstm: lengths must lie in [1, Lmax = %d] (got %d .. %d)" % (Lmax, int(ln.min()), int(ln.max())))
+        if int(rw.min()) < -1 or int(rw.max()) >= int(n_rows):
+            raise L.KbnerError("char_lstm: rows must be -1 or lie in [0, %d) (got %d .. %d)" % (int(n_rows), int(rw.min()), int(rw.max())))
+        named = rw[rw >= 0]
+        if named.unique().numel() != named.numel():
+            raise L.KbnerError("char_lstm: a row of the output matrix is named by more than one word")
+    return ch.to(I32).contiguous(), ln.to(I32).contiguous(), rw.to(I32).contiguous()
+
+
+class CharTables:
+    """checked word tables on the device, shared by the forward and the backward launch of one step"""
+
+    def __init__(self, chars, lens, rows, V, n_rows, device):
+        ch, ln, rw = check_char_tables(chars, lens, rows, V, n_rows)
+        self.W, self.Lmax, self.V, self.n_rows = ch.shape[0], max(ch.shape[1], 1), int(V), int(n_rows)
+        self.chars, self.lens, self.rows = (t.to(device) for t in (ch, ln, rw)) if self.W else (None, None, None)
+
+
+def _char_args(name, emb, wih, whh, bias_ih, bias_hh, tab, mat, col, n):
+    """shapes of the parameters and the block [col, col + 2Hc) inside the bf16 matrix `mat` -> E, Hc, ld"""
+    if emb.dim() != 2 or wih.dim() != 3 or whh.dim() != 3:
+        raise L.KbnerError("%s: emb f32 [V, E], wih f32 [2, 4Hc, E], whh f32 [2, 4Hc, Hc]" % name)
+    V, E = emb.shape
+    Hc = whh.shape[2]
+    if not (1 <= E <= CHAR_MAXD and 1 <= Hc <= CHAR_MAXD):
+        raise L.KbnerError("%s failed with code -22: 1 <= E, Hc <= %d (got E = %d, Hc = %d)" % (name, CHAR_MAXD, E, Hc))
+    if tuple(wih.shape) != (2, 4 * Hc, E) or tuple(whh.shape) != (2, 4 * Hc, Hc) or V != tab.V or \
+            any(b is not None and tuple(b.shape) != (2, 4 * Hc) for b in (bias_ih, bias_hh)):
+        raise L.KbnerError("%s: emb [V = %d, E], wih [2, 4Hc, E], whh [2, 4Hc, Hc], biases [2, 4Hc] (got %s, %s, %s)"
+                           % (name, tab.V, tuple(emb.shape), tuple(wih.shape), tuple(whh.shape)))
+    if not torch.is_tensor(mat) or mat.dtype != BF16 or mat.dim() != 2 or not mat.is_contiguous():
+        raise L.KbnerError("%s: the matrix must be a contiguous 2-d bfloat16 tensor" % name)
+    ld, col, n = mat.shape[1], int(col), int(n)
+    if col < 0 or col % 8 or ld % 8 or col + 2 * Hc > ld or (mat.data_ptr() + 2 * col) % 16:
+        raise L.KbnerError("%s: the block [col, col + 2Hc) = [%d, %d) must start at a multiple of 8, on a 16-byte boundary, and lie "
+                           "inside the %d columns of the matrix (a multiple of 8)" % (name, col, col + 2 * Hc, ld))
+    if mat.shape[0] < tab.n_rows or n < 1:
+        raise L.KbnerError("%s: the tables were checked against %d rows but the matrix holds %d; n >= 1" % (name, tab.n_rows, mat.shape[0]))
+    for t, nm in ((emb, "emb"), (wih, "wih"), (whh, "whh"), (bias_ih, "bias_ih"), (bias_hh, "bias_hh")):
+        if t is not None:
+            _chk(t, F32, nm)
+    if not mat.is_cuda or any(t is not None and t.device != mat.device for t in (emb, wih, whh, bias_ih, bias_hh, tab.chars)):
+        raise L.KbnerError("%s: the matrix, the parameters and the tables must be on one cuda device" % name)
+    return E, Hc, ld, col, n
+
+
+def char_lstm_ws(tab, Hc, device):
+    """the workspace kbner_char_lstm_fwd fills for kbner_char_lstm_bwd, f32"""
+    nbytes = L.load().kbner_char_lstm_ws_bytes(tab.W, tab.Lmax, int(Hc))
+    return torch.empty(max(nbytes // 4, 1), dtype=F32, device=device)
+
+
+def char_lstm_fwd(emb, wih, whh, bias_ih, bias_hh, tab, out2d, col, n, drop_e=NO_DROP, drop_l=NO_DROP, ws=None):
+    """The character BiLSTM block of FastCharacterEmbeddings, written into a column block (include/kbner.h kbner_char_lstm_fwd):
+    out2d[tab.rows[w], col:col + 2Hc] = bf16(h_fwd | h_bwd) of word w with the head's two pre-RNN dropout sites applied as
+    gather_rows_drop applies them to the same elements of out2d.  tab: CharTables (host-checked, then uploaded).  ws: char_lstm_ws(...)
+    to keep what char_lstm_bwd reads, None for a forward-only pass.  Nothing else of out2d is touched; no word, no launch."""
+    E, Hc, ld, col, n = _char_args("char_lstm_fwd", emb, wih, whh, bias_ih, bias_hh, tab, out2d, col, n)
+    if tab.W == 0:
+        return out2d
+    if ws is not None:
+        _chk(ws, F32, "ws")
+        if ws.numel() * 4 < L.load().kbner_char_lstm_ws_bytes(tab.W, tab.Lmax, Hc):
+            raise L.KbnerError("char_lstm_fwd: ws is smaller than kbner_char_lstm_ws_bytes asks for")
+    (se, te), (sl, tl) = drop_e, drop_l
+    L.call("kbner_char_lstm_fwd", ptr(emb), ptr(wih), ptr(whh), ptr(bias_ih), ptr(bias_hh), ptr(tab.chars), ptr(tab.lens), ptr(tab.rows),
+           c_void_p(out2d.data_ptr() + 2 * col), ld, col, ptr(ws), tab.W, tab.Lmax, tab.V, E, Hc, n, int(se) & 0xFFFFFFFF, int(te),
+           int(sl) & 0xFFFFFFFF, int(tl), stream_ptr())
+    return out2d
+
+
+def char_lstm_bwd(dout2d, col, emb, wih, whh, tab, ws, d_emb, d_wih, d_whh, d_bias_ih, d_bias_hh, n, drop_e=NO_DROP, drop_l=NO_DROP,
+                  key_col=None):
+    """Back-propagation through char_lstm_fwd (kbner_char_lstm_bwd): dout2d[:, col:col + 2Hc] is the gradient of the masked block; ADDS
+    to d_emb, d_wih, d_whh, d_bias_ih, d_bias_hh (f32, shaped as their parameters).  Same tables, sites and ws as the forward.
+    key_col: the block's column in the FORWARD's matrix (the mask keys) when dout2d is a narrower window of the gradient; default col."""
+    E, Hc, ld, col, n = _char_args("char_lstm_bwd", emb, wih, whh, None, None, tab, dout2d, col, n)
+    for g, p_, nm in ((d_emb, emb, "d_emb"), (d_wih, wih, "d_wih"), (d_whh, whh, "d_whh"), (d_bias_ih, None, "d_bias_ih"),
+                      (d_bias_hh, None, "d_bias_hh")):
+        _chk(g, F32, nm)
+        if g.numel() != (p_.numel() if p_ is not None else 8 * Hc) or g.device != dout2d.device:
+            raise L.KbnerError("char_lstm_bwd: %s must have its parameter's size, on the matrix's device" % nm)
+    if tab.W == 0:
+        return
+    _chk(ws, F32, "ws")
+    if ws.numel() * 4 < L.load().kbner_char_lstm_ws_bytes(tab.W, tab.Lmax, Hc):
+        raise L.KbnerError("char_lstm_bwd: ws is smaller than kbner_char_lstm_ws_bytes asks for")
+    (se, te), (sl, tl) = drop_e, drop_l
+    key_col = col if key_col is None else int(key_col)
+    if key_col < 0 or key_col % 8:
+        raise L.KbnerError("char_lstm_bwd: key_col is the forward's block column, a multiple of 8")
+    L.call("kbner_char_lstm_bwd", c_void_p(dout2d.data_ptr() + 2 * col), ld, key_col, ptr(emb), ptr(wih), ptr(whh), ptr(tab.chars),
+           ptr(tab.lens), ptr(tab.rows), ptr(ws), ptr(d_emb), ptr(d_wih), ptr(d_whh), ptr(d_bias_ih), ptr(d_bias_hh), tab.W, tab.Lmax,
+           tab.V, E, Hc, n, int(se) & 0xFFFFFFFF, int(te), int(sl) & 0xFFFFFFFF, int(tl), stream_ptr())
+
+
 def scatter_add_rows_ld(dout, col0, idx, dst, n, scale=1.0, drop_e=NO_DROP, drop_l=NO_DROP):
     """its backward for one source: dst[idx[r], :] += dout[r, col0:col0 + H] * m[r, col0:col0 + H] * scale for idx[r] >= 0 (unique
     indices; other rows untouched).  dout bf16 [R, ld], dst bf16 [*, H]; the masks are keyed by the column of the ld-wide row."""

@@ -19,7 +19,7 @@ import torch
 
 from . import lib as L_
 from . import ops
-from .lib import EPI_ATOMIC32, EPI_BIAS, GEMM_NT, GEMM_TN
+from .lib import EPI_ATOMIC32, EPI_BIAS, GEMM_NN, GEMM_NT, GEMM_TN
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -341,7 +341,7 @@ class BiLSTMHead:
         te, tl = ops.drop_thresh(self.dropout), ops.drop_thresh(self.locked_dropout)
         return word, ((int(sd[0]), te), (int(sd[1]), tl)), ((int(sd[2]), te), (int(sd[3]), tl))
 
-    def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw", source=None):
+    def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw", source=None, char=None):
         """One micro-batch of head training on constant features: forward, CRF NLL, and loss_scale * its gradient ADDED to self.g.
         X bf16 [rows, Dp] as new_input() lays it out -- or None with `source`, a FeatureStore.source() of the batch: the first stage
         (the pre-RNN dropouts and the padding to Dq) is then one kbner_gather_rows_blocks_drop from the stored rows; batch: the device dict of kbner.batch (ctags i32 [B, nc], clens i32 [B],
@@ -349,11 +349,14 @@ class BiLSTMHead:
         Sequence (sequence_tagger_model.py:959-964,969-994,1027 and the CRF loss): the three pre-RNN dropouts as one
         gather_rows_drop over X with an identity index (WordDropout: index -1), input GEMM, kbner_lstm_seq_train, the two post-RNN
         dropouts, head, compaction, CRF NLL forward / backward, and back through the same chain to kbner_lstm_seq_bwd and the weight
-        gradients.  Nothing flows into X.  -> the loss, a 0-d device tensor."""
+        gradients.  Nothing flows into X.  char: a CharStep (the trainable character BiLSTM's batch), or None: it writes its block
+        into the matrix the input GEMM reads, after the first stage has produced it, applying the pre-RNN sites itself; after the
+        recurrence's backward the block's window of dXt = dgx . Wih is handed to it.  -> the loss, a 0-d device tensor."""
         if self.arena is None:
             raise L_.KbnerError("this BiLSTMHead was not built for training (enable_training())")
         with L_.stream_scope():
             dev, Hp, T, R = self.device, self.Hp, self.T, B * n
+            X_in = X
             Mp = self.rows(B, n) if source is not None else X.shape[0]
             sites = self._draw_dropout(n) if drop == "draw" else drop
             self.last_drop = sites
@@ -377,6 +380,10 @@ class BiLSTMHead:
                     Xt[:, :self.Dp] = X
                 else:
                     Xt = X
+            if char is not None:
+                if Xt is X_in:       # no site drawn and no Dq pad: the caller's X would receive the block -- it never lives in X
+                    Xt = X_in.clone()
+                char.forward(Xt, sites, n)
             gx = torch.empty((Mp, 8 * Hp), dtype=BF16, device=dev)
             ops.gemm(GEMM_NT, Xt, self.wih_t, Mp, 8 * Hp, self.Dq, C=gx, bias=self.bias, epi=EPI_BIAS)
             out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
@@ -427,7 +434,109 @@ class BiLSTMHead:
             gw[1] += cross[4 * Hp:, Hp:]
             ops.colsum(dgx, self.grad("bias_ih"))
             ops.colsum(dgx, self.grad("bias_hh"))
+            if char is not None:
+                # the one window of dXt = dgx . Wih anything reads: the character block's columns.  The GEMM takes N in multiples of
+                # 128, so the window is CHAR_WINDOW columns of wih_t (leading dimension Dq) that contain the block.
+                assert self.Dq >= CHAR_WINDOW and self.Dq % CHAR_WINDOW == 0      # (Dq is Dp rounded up to 128: enable_training)
+                c0 = min(char.col, self.Dq - CHAR_WINDOW)
+                dwin = torch.empty((Mp, CHAR_WINDOW), dtype=BF16, device=dev)
+                ops.gemm(GEMM_NN, dgx, self.wih_t.reshape(-1)[c0:], Mp, CHAR_WINDOW, 8 * Hp, C=dwin, lda=8 * Hp, ldb=self.Dq)
+                char.backward(dwin, char.col - c0, n)
         return loss[0]
+
+
+CHAR_WINDOW = 128       # columns of the dXt window computed for the character block (the GEMM's N granule)
+
+
+class CharBiLSTM:
+    """The trainable parameters of FastCharacterEmbeddings on the device (flair/embeddings.py:670-758: char_embedding, char_layer): one
+    flat fp32 arena with a gradient buffer, in torch's layouts -- kbner_char_lstm_fwd / _bwd read them as they are, so there is no
+    shadow copy.  [ emb [V, E] | wih [2, 4Hc, E] | whh [2, 4Hc, Hc] | bias_ih [2, 4Hc] | bias_hh [2, 4Hc] ], all at the plain learning
+    rate (names containing 'embedding', finetune_trainer.py:552-553)."""
+    _FIELDS = ("emb", "wih", "whh", "bias_ih", "bias_hh")
+    _KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+    def __init__(self, state, device):
+        """state: {"char_embedding.weight", "char_layer.weight_ih_l0", ... "_reverse"} (FastCharacterEmbeddings.state_dict())"""
+        self.device = torch.device(device)
+        V, E = state["char_embedding.weight"].shape
+        Hc = state["char_layer.weight_hh_l0"].shape[1]
+        self.V, self.E, self.Hc = int(V), int(E), int(Hc)
+        self.shapes = {"emb": (V, E), "wih": (2, 4 * Hc, E), "whh": (2, 4 * Hc, Hc), "bias_ih": (2, 4 * Hc), "bias_hh": (2, 4 * Hc)}
+        self.offsets, off = {}, 0
+        for k in self._FIELDS:
+            self.offsets[k] = off
+            off += _round_up(int(np.prod(self.shapes[k])), 4)
+        self.n = off
+        self.arena = torch.zeros(self.n, dtype=F32, device=self.device)
+        self.g = torch.zeros(self.n, dtype=F32, device=self.device)
+        self.load_state(state)
+
+    def param(self, name, buf=None):
+        buf = self.arena if buf is None else buf
+        o, shp = self.offsets[name], self.shapes[name]
+        return buf[o:o + int(np.prod(shp))].view(shp)
+
+    def grad(self, name):
+        return self.param(name, self.g)
+
+    def load_state(self, state):
+        f = lambda k: torch.as_tensor(state[k]).detach().float().cpu()   # noqa: E731
+        parts = {"emb": f("char_embedding.weight")}
+        for name, key in zip(self._FIELDS[1:], self._KEYS):
+            parts[name] = torch.stack([f("char_layer." + key), f("char_layer." + key + "_reverse")])
+        for k, v in parts.items():
+            if tuple(v.shape) != tuple(self.shapes[k]):
+                raise ValueError("character state: %s is %s, this embedding's is %s" % (k, tuple(v.shape), tuple(self.shapes[k])))
+            self.param(k).copy_(v.to(self.device))
+        self.g.zero_()
+
+    def state(self, buf=None):
+        """the arena (or a buffer laid out like it) under the reference's parameter names (host float32)"""
+        p = {k: self.param(k, buf).detach().cpu() for k in self._FIELDS}
+        out = {"char_embedding.weight": p["emb"].clone()}
+        for name, key in zip(self._FIELDS[1:], self._KEYS):
+            out["char_layer." + key] = p[name][0].clone()
+            out["char_layer." + key + "_reverse"] = p[name][1].clone()
+        return out
+
+
+class CharStep:
+    """One batch of the character BiLSTM inside a step of the head: the host word tables (FastCharacterEmbeddings.char_batch), the
+    block's column, and what the forward saved for the backward.  The placement rule: the block is written into the matrix the input
+    GEMM reads -- Xt while training (its columns arrive there as zeros), X itself in a forward-only pass -- never into the stored
+    features; the kernel applies the pre-RNN masks itself."""
+
+    def __init__(self, net, chars, lens, rows, col):
+        self.net, self.col = net, int(col)
+        self.chars, self.lens, self.rows = chars, lens, np.asarray(rows)
+        self.tab = self.ws = self.sites = None
+
+    def _params(self):
+        return [self.net.param(k) for k in CharBiLSTM._FIELDS]
+
+    def forward(self, Xt, sites, n, save=True):
+        """sites: None or (word: WordDropout positions bool [n] or None, (element site, locked site), ...) as the head draws them"""
+        rows, se, sl = self.rows, ops.NO_DROP, ops.NO_DROP
+        if sites is not None:
+            word, (se, sl) = sites[0], sites[1]
+            if word is not None:
+                live = rows >= 0
+                rows = np.where(live & np.asarray(word, bool)[np.where(live, rows, 0) % n], -1, rows)
+        self.tab = ops.CharTables(self.chars, self.lens, rows, self.net.V, Xt.shape[0], Xt.device)
+        self.sites = (se, sl)
+        self.ws = ops.char_lstm_ws(self.tab, self.net.Hc, Xt.device) if save and self.tab.W else None
+        ops.char_lstm_fwd(*self._params(), self.tab, Xt, self.col, n, se, sl, ws=self.ws)
+
+    def backward(self, dwin, col, n):
+        """dwin bf16 [rows, *]: the gradient of the matrix the forward wrote into, its block at column `col` of dwin"""
+        net = self.net
+        p = self._params()
+        tab = self.tab
+        if dwin.shape[0] < tab.n_rows:
+            raise L_.KbnerError("CharStep.backward: the gradient window holds fewer rows than the forward's matrix")
+        ops.char_lstm_bwd(dwin, col, p[0], p[1], p[2], tab, self.ws, *[net.grad(k) for k in CharBiLSTM._FIELDS], n, self.sites[0],
+                          self.sites[1], key_col=self.col)
 
 
 class FeatureStore:
@@ -654,11 +763,27 @@ class StackOptimizer:
         self.norm_sq = torch.zeros(1, dtype=F32, device=head.device)
         self.reset()
 
+    @property
+    def char(self):
+        """the head's character BiLSTM (CharBiLSTM) or None: its arena is one more range of the plain-learning-rate group"""
+        return getattr(self.head, "char", None)
+
+    def groups(self):
+        """[(name, parameters, learning rate)]: what step() updates, in order"""
+        h = self.head
+        out = [("rnn+transitions", h.split, self.lr * self.lr_rate * self.lr_scale), ("linear", h.n - h.split, self.lr * self.lr_scale)]
+        if self.char is not None:
+            out.append(("char", self.char.n, self.lr * self.lr_scale))
+        return out
+
     def reset(self):
         """drop the moments (a new state was loaded into the head)"""
         h = self.head
         self.m = torch.zeros(h.n, dtype=F32, device=h.device) if self.name == "AdamW" else None
         self.v = torch.zeros(h.n, dtype=F32, device=h.device) if self.name == "AdamW" else None
+        c = self.char
+        self.cm = torch.zeros(c.n, dtype=F32, device=h.device) if (c is not None and self.name == "AdamW") else None
+        self.cv = torch.zeros(c.n, dtype=F32, device=h.device) if (c is not None and self.name == "AdamW") else None
         self.t = 0
 
     def step(self, grad_scale=1.0):
@@ -666,6 +791,9 @@ class StackOptimizer:
         h = self.head
         with L_.stream_scope():
             ops.grad_sqnorm(h.g, self.ws, self.norm_sq)
+            c = self.char
+            if c is not None:      # ONE clip norm over head and character gradients (clip_grad_norm_(model.parameters()))
+                ops.grad_sqnorm(c.g, self.ws, self.norm_sq, accumulate=True)
             self.t += 1
             b1, b2 = self.betas
             bc = (1.0 - b2 ** self.t) ** 0.5 / (1.0 - b1 ** self.t)
@@ -677,6 +805,15 @@ class StackOptimizer:
                               self.norm_sq, self.max_norm, grad_scale, True)
                 else:
                     ops.sgd(h.arena[lo:hi], h.g[lo:hi], sh, nsh, lr, self.norm_sq, self.max_norm, grad_scale, True)
+            if c is not None:
+                lr = self.lr * self.lr_scale
+                if self.name == "AdamW":
+                    if self.cm is None or self.cm.numel() != c.n:
+                        self.cm, self.cv = torch.zeros_like(c.g), torch.zeros_like(c.g)
+                    ops.adamw(c.arena, c.g, self.cm, self.cv, None, 0, lr * bc, 0.0, b1, b2, self.eps, self.norm_sq, self.max_norm,
+                              grad_scale, True)
+                else:
+                    ops.sgd(c.arena, c.g, None, 0, lr, self.norm_sq, self.max_norm, grad_scale, True)
             h._refresh()
         return self.norm_sq
 
