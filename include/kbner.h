@@ -450,6 +450,18 @@ int kbner_lstm_seq_train(const kbner_bf16* gx, int ld_gx, const int* gxi, const 
 int kbner_lstm_seq_bwd(const kbner_bf16* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const kbner_bf16* whht,
                        const kbner_bf16* gates, const float* cs, float* dc_carry, kbner_bf16* dgx, int ld_dgx, int steps, int B,
                        int Hp, int ndir, void* stream);
+/* The same walk for a recurrence that started from a state: the forward kernels read h[0] = h_0 and c = c_0 on entry and save
+ * hprev = h_0 at step 0 (so the weight-gradient product dgx^T hprev holds the h_0 term).
+ *   c0  f32 [ndir, B, Hp] or NULL: c_prev of step 0 is c0[d, b, :] (NULL: 0)
+ *   dh0 f32 [ndir, B, Hp] or NULL: after step 0 one more launch of the recurrent product alone (the step kernel's MFMA loop and
+ *       batch dispatch, no gate arithmetic) writes dh0[d, b, :] = dgx[gxi[0, d, b], d-block] . Whh_d in f32 -- the gradient of
+ *       h_0 -- for every (d, b) with gxi[0, d, b] >= 0; other entries are untouched
+ * On return dc_carry is the gradient of c_0.  With c0 == NULL and dh0 == NULL the launches, dgx and dc_carry are those of
+ * kbner_lstm_seq_bwd bit for bit.  steps == 0 launches nothing and writes nothing.  Constraints and argument checks
+ * (-22, nothing written) as kbner_lstm_seq_bwd. */
+int kbner_lstm_seq_bwd_init(const kbner_bf16* dout, int ldo, const int* out_col, const int* outi, const int* gxi,
+                            const kbner_bf16* whht, const kbner_bf16* gates, const float* cs, const float* c0, float* dc_carry,
+                            kbner_bf16* dgx, int ld_dgx, float* dh0, int steps, int B, int Hp, int ndir, void* stream);
 
 /* ---------------- character BiLSTM of FastCharacterEmbeddings (csrc/char_lstm.hip) ---------------- */
 /* flair/embeddings.py:670-758: torch.nn.Embedding -> one-layer bidirectional torch.nn.LSTM over every word's characters

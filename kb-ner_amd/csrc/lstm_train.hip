@@ -3,16 +3,19 @@
 // Two entry points next to csrc/lstm.hip, whose kernels stay as they are:
 //   kbner_lstm_seq_train  the forward recurrence of kbner_lstm_seq that also keeps, per consumed gx row, what the backward pass
 //                         needs: the post-activation gates, c_t and the h_{t-1} row it multiplied;
-//   kbner_lstm_seq_bwd    back-propagation through time: one launch per time step from the last step to the first.
+//   kbner_lstm_seq_bwd    back-propagation through time: one launch per time step from the last step to the first;
+//   kbner_lstm_seq_bwd_init  the same walk for a recurrence started from a given state: c_prev of step 0 is c_0, and one more launch
+//                         of the recurrent product alone produces the gradient of h_0.
 //
 // TRAINING CONTRACT of the row tables (gxi / outi i32 [steps, ndir, B]): prefix-active -- every (direction, sequence) is active
 // (gxi >= 0) for steps 0 .. len - 1 and finished (-1) after -- and no (direction, gx row) is consumed twice: the saved state and
 // dgx are kept per gx row.  kbner.stack.step_tables produces this form; the host wrapper checks it before upload, the library
-// cannot (the tables live in device memory).  h_0 = c_0 = 0 (no gradient flows into an initial state).
+// cannot (the tables live in device memory).  The forward starts from whatever h[0] and c hold on entry; kbner_lstm_seq_bwd takes
+// them to be 0 (no gradient flows into an initial state), kbner_lstm_seq_bwd_init takes c_0 and returns d h_0 and d c_0.
 //
 // Backward step s for an active (d, b), with r = gxi[s], nx = gxi[s + 1] (-1 past the end or when finished), pv = gxi[s - 1]:
 //   dh  = dout[outi[s]] (0 where outi < 0) + (nx >= 0 ? dgx[nx, d-block] . Whh_d : 0)          (sum over the 4Hp gate columns)
-//   t   = tanh(c[r]) ;  c_prev = pv >= 0 ? c[pv] : 0
+//   t   = tanh(c[r]) ;  c_prev = pv >= 0 ? c[pv] : c_0   (c_0 = 0 without an initial state)
 //   dc  = dc_carry + dh o (1 - t^2)
 //   di  = dc g i (1 - i) ;  df = dc c_prev f (1 - f) ;  dg = dc i (1 - g^2) ;  do = dh t o (1 - o)
 //   dc_carry = dc f ;  dgx[r, d-block] = (di, df, dg, do)   (bf16)
@@ -171,13 +174,17 @@ static void lstm_seq_train_launch(const bf16_t* gx, int ld_gx, const int* gxi, c
 //   gxi / gxi_next / gxi_prev / outi i32 [ndir, B] : this step's tables and its neighbours' (null at either end)
 //   whht  bf16 [ndir, Hp, 4Hp] ; gates / cs as the forward saved them ; dc_carry f32 [ndir, B, Hp] in place
 //   dgx   bf16 [rows_gx, ld_dgx] : row nx read (written by the previous launch), row r written
-template <int NT>
+//   c0    f32 [ndir, B, Hp] or null : c_prev where gxi_prev gives none (the launch of step 0 alone passes it)
+// H0 = true is the launch AFTER step 0: gxi_next = gxi = the tables of step 0, the same product dgx[gxi[0], d-block] . Whh_d and
+// reduction, and the f32 sum goes to dh0 f32 [ndir, B, Hp] for every active (d, b); no gate arithmetic, nothing else is written.
+template <int NT, bool H0>
 __global__ __launch_bounds__(256) void lstm_seq_bwd_step_kernel(const bf16_t* __restrict__ dout, int ldo, const int* __restrict__ out_col,
                                                                const int* __restrict__ outi, const int* __restrict__ gxi,
                                                                const int* __restrict__ gxi_next, const int* __restrict__ gxi_prev,
                                                                const bf16_t* __restrict__ whht, const bf16_t* __restrict__ gates,
                                                                const float* __restrict__ cs, float* __restrict__ dc_carry,
-                                                               bf16_t* dgx, int ld_dgx, int B, int Hp, int ndir) {
+                                                               bf16_t* dgx, int ld_dgx, int B, int Hp, int ndir,
+                                                               const float* __restrict__ c0, float* __restrict__ dh0) {
   __shared__ f4v red[4 * NT * 64];
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
@@ -242,6 +249,11 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_step_kernel(const bf16_t* __
     dh[2] += p[2];
     dh[3] += p[3];
   }
+  const size_t sidx = ((size_t)d * B + b) * Hp + j0 + g * 4;
+  if constexpr (H0) {
+    *reinterpret_cast<float4*>(dh0 + sidx) = make_float4(dh[0], dh[1], dh[2], dh[3]);
+    return;
+  }
   const int orow = outi[d * B + b];
   if (orow >= 0) {
     const uint2 u = *reinterpret_cast<const uint2*>(dout + (size_t)orow * ldo + out_col[d] + j0 + g * 4);
@@ -265,8 +277,9 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_step_kernel(const bf16_t* __
   const size_t coff = (size_t)d * Hp + j0 + g * 4;
   const float4 cv = *reinterpret_cast<const float4*>(cs + (size_t)row * ndir * Hp + coff);
   const int pv = gxi_prev != nullptr ? gxi_prev[d * B + b] : -1;
-  const float4 cpv = pv >= 0 ? *reinterpret_cast<const float4*>(cs + (size_t)pv * ndir * Hp + coff) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const size_t sidx = ((size_t)d * B + b) * Hp + j0 + g * 4;
+  const float4 cpv = pv >= 0           ? *reinterpret_cast<const float4*>(cs + (size_t)pv * ndir * Hp + coff)
+                     : c0 != nullptr ? *reinterpret_cast<const float4*>(c0 + sidx)
+                                     : make_float4(0.f, 0.f, 0.f, 0.f);
   const float4 carry = *reinterpret_cast<const float4*>(dc_carry + sidx);
   const float cc[4] = {cv.x, cv.y, cv.z, cv.w}, cp[4] = {cpv.x, cpv.y, cpv.z, cpv.w};
   float dcn[4] = {carry.x, carry.y, carry.z, carry.w}, dg4[4][4];
@@ -292,12 +305,50 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_step_kernel(const bf16_t* __
   }
 }
 
-template <int NT>
+template <int NT, bool H0>
 static void lstm_seq_bwd_launch(const bf16_t* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const int* gxi_next,
                                 const int* gxi_prev, const bf16_t* whht, const bf16_t* gates, const float* cs, float* dc_carry,
-                                bf16_t* dgx, int ld_dgx, int B, int Hp, int ndir, hipStream_t stream) {
-  hipLaunchKernelGGL(lstm_seq_bwd_step_kernel<NT>, dim3(Hp / 16, ndir, (B + 16 * NT - 1) / (16 * NT)), dim3(256), 0, stream, dout, ldo,
-                     out_col, outi, gxi, gxi_next, gxi_prev, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir);
+                                bf16_t* dgx, int ld_dgx, int B, int Hp, int ndir, const float* c0, float* dh0, hipStream_t stream) {
+  hipLaunchKernelGGL((lstm_seq_bwd_step_kernel<NT, H0>), dim3(Hp / 16, ndir, (B + 16 * NT - 1) / (16 * NT)), dim3(256), 0, stream, dout,
+                     ldo, out_col, outi, gxi, gxi_next, gxi_prev, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, c0, dh0);
+}
+
+template <bool H0>
+static void lstm_seq_bwd_dispatch(const bf16_t* dout, int ldo, const int* out_col, const int* oi, const int* gi, const int* gn,
+                                  const int* gp, const bf16_t* whht, const bf16_t* gates, const float* cs, float* dc_carry, bf16_t* dgx,
+                                  int ld_dgx, int B, int Hp, int ndir, const float* c0, float* dh0, hipStream_t st) {
+  if (B <= 16)
+    lstm_seq_bwd_launch<1, H0>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, c0, dh0, st);
+  else if (B <= 32)
+    lstm_seq_bwd_launch<2, H0>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, c0, dh0, st);
+  else if (B <= 48)
+    lstm_seq_bwd_launch<3, H0>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, c0, dh0, st);
+  else
+    lstm_seq_bwd_launch<4, H0>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, c0, dh0, st);
+}
+
+// the walk of kbner_lstm_seq_bwd and kbner_lstm_seq_bwd_init: c0 reaches the launch of step 0 alone, dh0 adds one launch after it
+static int lstm_seq_bwd_run(const bf16_t* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const bf16_t* whht,
+                            const bf16_t* gates, const float* cs, const float* c0, float* dc_carry, bf16_t* dgx, int ld_dgx, float* dh0,
+                            int steps, int B, int Hp, int ndir, void* stream) {
+  KBNER_CHECK_ARG(dout != nullptr && out_col != nullptr && outi != nullptr && gxi != nullptr && whht != nullptr && gates != nullptr &&
+                  cs != nullptr && dc_carry != nullptr && dgx != nullptr);
+  KBNER_CHECK_ARG(steps >= 0 && B > 0 && ndir > 0 && Hp > 0 && Hp % 64 == 0 && ldo % 4 == 0 && ld_dgx % 8 == 0 &&
+                  (long long)ld_dgx >= (long long)ndir * 4 * Hp);
+  const int per = ndir * B;
+  hipStream_t st = (hipStream_t)stream;
+  for (int s = steps - 1; s >= 0; --s) {
+    const int* gi = gxi + (size_t)s * per;
+    const int* gn = s + 1 < steps ? gi + per : nullptr;
+    const int* gp = s > 0 ? gi - per : nullptr;
+    const int* oi = outi + (size_t)s * per;
+    lstm_seq_bwd_dispatch<false>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir,
+                                 s == 0 ? c0 : nullptr, nullptr, st);
+  }
+  if (steps > 0 && dh0 != nullptr)
+    lstm_seq_bwd_dispatch<true>(dout, ldo, out_col, outi, gxi, gxi, nullptr, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, nullptr,
+                                dh0, st);
+  KBNER_LAUNCH_RET();
 }
 
 extern "C" {
@@ -341,27 +392,19 @@ int kbner_lstm_seq_train(const bf16_t* gx, int ld_gx, const int* gxi, const bf16
 int kbner_lstm_seq_bwd(const bf16_t* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const bf16_t* whht,
                        const bf16_t* gates, const float* cs, float* dc_carry, bf16_t* dgx, int ld_dgx, int steps, int B, int Hp,
                        int ndir, void* stream) {
-  KBNER_CHECK_ARG(dout != nullptr && out_col != nullptr && outi != nullptr && gxi != nullptr && whht != nullptr && gates != nullptr &&
-                  cs != nullptr && dc_carry != nullptr && dgx != nullptr);
-  KBNER_CHECK_ARG(steps >= 0 && B > 0 && ndir > 0 && Hp > 0 && Hp % 64 == 0 && ldo % 4 == 0 && ld_dgx % 8 == 0 &&
-                  (long long)ld_dgx >= (long long)ndir * 4 * Hp);
-  const int per = ndir * B;
-  hipStream_t st = (hipStream_t)stream;
-  for (int s = steps - 1; s >= 0; --s) {
-    const int* gi = gxi + (size_t)s * per;
-    const int* gn = s + 1 < steps ? gi + per : nullptr;
-    const int* gp = s > 0 ? gi - per : nullptr;
-    const int* oi = outi + (size_t)s * per;
-    if (B <= 16)
-      lstm_seq_bwd_launch<1>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, st);
-    else if (B <= 32)
-      lstm_seq_bwd_launch<2>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, st);
-    else if (B <= 48)
-      lstm_seq_bwd_launch<3>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, st);
-    else
-      lstm_seq_bwd_launch<4>(dout, ldo, out_col, oi, gi, gn, gp, whht, gates, cs, dc_carry, dgx, ld_dgx, B, Hp, ndir, st);
-  }
-  KBNER_LAUNCH_RET();
+  return lstm_seq_bwd_run(dout, ldo, out_col, outi, gxi, whht, gates, cs, nullptr, dc_carry, dgx, ld_dgx, nullptr, steps, B, Hp, ndir,
+                          stream);
+}
+
+// kbner_lstm_seq_bwd for a recurrence that started from a state (h_0, c_0) instead of zeros.
+//   c0  f32 [ndir, B, Hp] or null: the c the forward started from; c_prev of step 0 (null: 0)
+//   dh0 f32 [ndir, B, Hp] or null: receives, after step 0, dgx[gxi[0, d, b], d-block] . Whh_d -- the gradient of h_0 -- for every
+//       (d, b) with gxi[0, d, b] >= 0; other entries are untouched
+// dc_carry on return is the gradient of c_0.  With c0 and dh0 null: the launches and results of kbner_lstm_seq_bwd.
+int kbner_lstm_seq_bwd_init(const bf16_t* dout, int ldo, const int* out_col, const int* outi, const int* gxi, const bf16_t* whht,
+                            const bf16_t* gates, const float* cs, const float* c0, float* dc_carry, bf16_t* dgx, int ld_dgx, float* dh0,
+                            int steps, int B, int Hp, int ndir, void* stream) {
+  return lstm_seq_bwd_run(dout, ldo, out_col, outi, gxi, whht, gates, cs, c0, dc_carry, dgx, ld_dgx, dh0, steps, B, Hp, ndir, stream);
 }
 
 }  // extern "C"

@@ -32,8 +32,16 @@ STOP_TAG: str = "<STOP>"
 _UNSUPPORTED_TRUE = ("use_mfvi", "use_cnn", "biaf_attention", "use_language_attention",
                      "token_level_attention", "posterior_constraint", "use_language_vector", "enhanced_crf",
                      "use_language_id", "use_transition_attention", "unlabel_entropy_loss", "relearn_embeddings", "map_embeddings",
-                     "no_encoder", "new_drop", "use_embedding_masks", "use_gumbel", "embedding_attention",
-                     "train_initial_hidden_state")
+                     "no_encoder", "new_drop", "use_embedding_masks", "use_gumbel", "embedding_attention")
+
+
+_LOGGED_ONCE = set()
+
+
+def _log_once(key, msg, *args):
+    if key not in _LOGGED_ONCE:
+        _LOGGED_ONCE.add(key)
+        log.info(msg, *args)
 
 
 NARROW_MAX_TAGS = 64    # one tag per lane of one wave: the softmax head and every distillation kernel (those at 32)
@@ -76,8 +84,13 @@ class SequenceTagger(flair.nn.Model):
             if crf_only:
                 raise NotImplementedError("use_crf=False (softmax head) with %s: these losses / decoders are implemented on the CRF "
                                           "only" % ", ".join(crf_only))
-        if use_rnn and rnn_layers != 1:
-            raise NotImplementedError("rnn_layers > 1 is not implemented (the KB-NER / ACE configs use the default of 1)")
+        # the BiLSTM's own switches (:317-357): any number of layers (torch.nn.LSTM(num_layers), dropout 0.5 between them) and the
+        # trained initial state lstm_init_h / lstm_init_c; without use_rnn they are accepted and select nothing, as in the reference
+        if isinstance(rnn_layers, bool) or int(rnn_layers) != rnn_layers or int(rnn_layers) < 1:
+            raise ValueError("rnn_layers must be an integer >= 1 (got %r)" % (rnn_layers,))
+        if not use_rnn and (int(rnn_layers) != 1 or train_initial_hidden_state):
+            _log_once("rnn switches without use_rnn", "rnn_layers=%r / train_initial_hidden_state=%r have no effect without use_rnn: "
+                      "there is no BiLSTM", rnn_layers, bool(train_initial_hidden_state))
         # multi-view ("cooperative learning") training: the shipped *_multiview_posterior_* YAMLs set multi_view_training +
         # distill_posterior + temperature; the distill_exact branch and the calculate_l2_loss / l2_loss_only terms of
         # _calculate_multi_view_loss are implemented too (the unlabeled-data branch is not: use_unlabeled_data is refused)
@@ -144,6 +157,7 @@ class SequenceTagger(flair.nn.Model):
         self.tagset_size = len(tag_dictionary)
         self.use_crf = bool(use_crf)
         self.use_rnn = bool(use_rnn)
+        self.nlayers, self.train_initial_hidden_state = int(rnn_layers), bool(train_initial_hidden_state)
         self.use_cnn = False
         self.sentence_level_loss = sentence_loss
         self.remove_x = remove_x
@@ -295,7 +309,16 @@ class SequenceTagger(flair.nn.Model):
         tr[self.start_idx, :] = -1e12
         tr[:, self.stop_idx] = -1e12
         self._stack_blocks = blocks
-        self.load_stack_state({"rnn": rnn, "linear.weight": u(T, 2 * H, b=kl), "linear.bias": u(T, b=kl), "transitions": tr}, _init=True)
+        st = {"rnn": rnn, "linear.weight": u(T, 2 * H, b=kl), "linear.bias": u(T, b=kl), "transitions": tr}
+        # the layers above the first (they read 2H columns) and the initial state are drawn after everything a one-layer tagger draws
+        for layer in range(1, self.nlayers):
+            for sfx in ("", "_reverse"):
+                rnn["weight_ih_l%d%s" % (layer, sfx)], rnn["weight_hh_l%d%s" % (layer, sfx)] = u(4 * H, 2 * H), u(4 * H, H)
+                rnn["bias_ih_l%d%s" % (layer, sfx)], rnn["bias_hh_l%d%s" % (layer, sfx)] = u(4 * H), u(4 * H)
+        if self.train_initial_hidden_state:     # torch.randn(nlayers * 2, hidden) each (:346-357)
+            st["lstm_init_h"] = torch.randn(2 * self.nlayers, H, generator=g)
+            st["lstm_init_c"] = torch.randn(2 * self.nlayers, H, generator=g)
+        self.load_stack_state(st, _init=True)
         self._encoders = {}
 
     def _char_net(self):
@@ -336,10 +359,27 @@ class SequenceTagger(flair.nn.Model):
             if not has and ("char" in state or "char_dictionary" in state):
                 raise ValueError("load_stack_state: the state carries character parameters ('char', 'char_dictionary') but this "
                                  "tagger's embedding list has no FastCharacterEmbeddings")
+        from kbner.stack import rnn_layer_count
+        theirs_l = int(state.get("rnn_layers", rnn_layer_count(state["rnn"])))
+        theirs_i = bool(state.get("train_initial_hidden_state", "lstm_init_h" in state))
+        if theirs_l != rnn_layer_count(state["rnn"]) or theirs_i != ("lstm_init_h" in state and "lstm_init_c" in state):
+            raise ValueError("load_stack_state: the state says rnn_layers=%d, train_initial_hidden_state=%s but holds %d BiLSTM layer(s) "
+                             "and %s lstm_init_h / lstm_init_c" % (theirs_l, theirs_i, rnn_layer_count(state["rnn"]),
+                                                                  "both" if "lstm_init_h" in state and "lstm_init_c" in state else "not both"))
+        if theirs_l != self.nlayers:
+            raise ValueError("load_stack_state: the state holds a BiLSTM of rnn_layers=%d, this tagger was built with rnn_layers=%d"
+                             % (theirs_l, self.nlayers))
+        if theirs_i != self.train_initial_hidden_state:
+            raise ValueError("load_stack_state: the state was saved with train_initial_hidden_state=%s (it %s lstm_init_h / lstm_init_c), "
+                             "this tagger was built with train_initial_hidden_state=%s"
+                             % (theirs_i, "carries" if theirs_i else "has no", self.train_initial_hidden_state))
         st = {"rnn": {k: torch.as_tensor(v).detach().float().cpu() for k, v in state["rnn"].items()},
               "linear.weight": torch.as_tensor(state["linear.weight"]).detach().float().cpu(),
               "linear.bias": torch.as_tensor(state["linear.bias"]).detach().float().cpu(),
               "transitions": torch.as_tensor(state["transitions"]).detach().float().cpu()}
+        if theirs_i:
+            st["lstm_init_h"] = torch.as_tensor(state["lstm_init_h"]).detach().float().cpu()
+            st["lstm_init_c"] = torch.as_tensor(state["lstm_init_c"]).detach().float().cpu()
         D, got = sum(self._stack_blocks), int(st["rnn"]["weight_ih_l0"].shape[1])
         if got != D:       # (refused before anything is replaced: deep inside the head it would be a shape error without a name)
             raise ValueError("load_stack_state: weight_ih_l0 reads %d input columns but this stack's embeddings are %d wide (blocks %s): "
@@ -366,8 +406,13 @@ class SequenceTagger(flair.nn.Model):
             if getattr(self, "stack_optimizer", None) is not None:
                 self.stack_optimizer.reset()
             return
-        self.stack_head = K.BiLSTMHead(st["rnn"], st["linear.weight"], st["linear.bias"], self._stack_blocks, self.hidden_size,
-                                       flair.device)
+        if self.nlayers == 1 and not theirs_i:
+            self.stack_head = K.BiLSTMHead(st["rnn"], st["linear.weight"], st["linear.bias"], self._stack_blocks, self.hidden_size,
+                                           flair.device)
+        else:
+            self.stack_head = K.BiLSTMHead(st["rnn"], st["linear.weight"], st["linear.bias"], self._stack_blocks, self.hidden_size,
+                                           flair.device, rnn_layers=self.nlayers,
+                                           init_state={k: st[k] for k in ("lstm_init_h", "lstm_init_c")} if theirs_i else None)
         self._transitions = st["transitions"].to(flair.device).contiguous()
 
     @property
@@ -375,6 +420,9 @@ class SequenceTagger(flair.nn.Model):
         """the stack's weights in the reference's layout; of a trainable tagger: read from the parameter arena"""
         head = getattr(self, "stack_head", None)
         st = head.state() if (head is not None and head.arena is not None) else self.__dict__["_stack_state_host"]
+        if self.__dict__.get("nlayers", 1) != 1 or self.__dict__.get("train_initial_hidden_state", False):
+            # (a one-layer tagger from zeros writes the keys it always wrote; a state without these two loads as 1 / False)
+            st = dict(st, rnn_layers=self.nlayers, train_initial_hidden_state=self.train_initial_hidden_state)
         if self.__dict__.get("_char_slot") is not None and "_stack_embs" in self.__dict__:
             st = dict(st)
             st["char"] = self._char_net().state()
@@ -627,8 +675,12 @@ class SequenceTagger(flair.nn.Model):
             yield "transitions", self.transitions
             yield "linear.weight", self._stack_state["linear.weight"]
             yield "linear.bias", self._stack_state["linear.bias"]
-            for k, v in self._stack_state["rnn"].items():
+            st = self._stack_state
+            for k, v in st["rnn"].items():
                 yield "rnn." + k, v
+            for k in ("lstm_init_h", "lstm_init_c"):      # (train_initial_hidden_state)
+                if k in st:
+                    yield k, st[k]
             if self.__dict__.get("_char_slot") is not None:     # (names containing 'embedding': the plain learning-rate group)
                 embs = list(self.embeddings.embeddings) if hasattr(self.embeddings, "embeddings") else [self.embeddings]
                 idx = embs.index(self._stack_embs[self._char_slot])
@@ -648,7 +700,7 @@ class SequenceTagger(flair.nn.Model):
 
     def zero_grad(self, set_to_none=False):
         if getattr(self, "stack_head", None) is not None and self.stack_head.arena is not None:
-            self.stack_head.g.zero_()
+            self.stack_head.zero_grad()
             if getattr(self.stack_head, "char", None) is not None:
                 self.stack_head.char.g.zero_()
         if self.engine is not None and self.engine.arena.g is not None:    # None: a teacher after drop_gradients()
@@ -1271,7 +1323,8 @@ class SequenceTagger(flair.nn.Model):
             "linear.bias": self.engine.arena.param("linear.bias").detach().cpu().clone(),
             "transitions": self.engine.arena.param("transitions").detach().cpu().clone(),
             "tag_dictionary": self.tag_dictionary, "tag_type": self.tag_type, "hidden_size": self.hidden_size,
-            "use_crf": self.use_crf, "use_rnn": False, "remove_x": self.remove_x, "sentence_loss": self.sentence_level_loss,
+            "use_crf": self.use_crf, "use_rnn": False, "rnn_layers": self.nlayers,
+            "train_initial_hidden_state": self.train_initial_hidden_state, "remove_x": self.remove_x, "sentence_loss": self.sentence_level_loss,
             "word_dropout": self.use_word_dropout, "dropout": self.use_dropout, "locked_dropout": self.use_locked_dropout,
             "embedding_model_dir": getattr(self._emb, "name", None),
             "embedding_layers": getattr(self._emb, "layers", "-1"), "embedding_scalar_mix": bool(getattr(self._emb, "use_scalar_mix", False)),
@@ -1296,7 +1349,8 @@ class SequenceTagger(flair.nn.Model):
                     dropout=state.get("dropout", 0.0), locked_dropout=state.get("locked_dropout", 0.0), temperature=state.get("temperature", 1),
                     **{k: state.get(k, False) for k in ("multi_view_training", "distill_posterior", "distill_crf", "distill_exact",
                                                         "crf_attention", "distill_with_gold", "exp_score", "calculate_l2_loss", "l2_loss_only")},
-                    gold_const=state.get("gold_const", 1.0))
+                    gold_const=state.get("gold_const", 1.0), rnn_layers=int(state.get("rnn_layers", 1)),
+                    train_initial_hidden_state=bool(state.get("train_initial_hidden_state", False)))
         model.engine.load_hf_state_dict(state["encoder_state_dict"])
         for k in ("linear.weight", "linear.bias", "transitions"):
             model.engine.set_param(k, state[k])

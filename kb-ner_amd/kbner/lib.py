@@ -87,6 +87,7 @@ SIGNATURES = {
     "kbner_lstm_seq": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "kbner_lstm_seq_train": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P]),
     "kbner_lstm_seq_bwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "kbner_lstm_seq_bwd_init": (c_int, [P, c_int, P, P, P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     "kbner_char_lstm_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "kbner_char_lstm_fwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, U32, U32, U32,
                                     U32, P]),

@@ -4,7 +4,8 @@ libkbner_hip.so.
 
 Reference path (restated): FastSequenceTagger.forward with `use_rnn` (flair/models/sequence_tagger_model.py:844-1052):
     sentence_tensor = cat([features[name] * selection[idx] for idx, name in enumerate(sorted(features))], -1)   (:879-891)
-    packed BiLSTM (torch.nn.LSTM(D, hidden, 1 layer, bidirectional), :324-357, :969-994) -> linear(2 * hidden -> T) (:1027)
+    packed BiLSTM (torch.nn.LSTM(D, hidden, rnn_layers, bidirectional, dropout 0.5 between layers), optionally started from the trained
+    lstm_init_h / lstm_init_c, :317-357, :969-994) -> linear(2 * hidden -> T) (:1027)
 and the feature producers: TransformerWordEmbeddings (frozen, first-sub-token pooling, optionally `use_internal_doc`:
 embeddings.py:3116-3117,3283-3284) and FlairEmbeddings (character LM hidden state at each token's end,
 embeddings.py:2469-2543, flair/models/language_model.py:71-138).
@@ -54,17 +55,28 @@ class LSTMGroup:
             out[q * self.Hp:q * self.Hp + self.H] = t[q * self.H:(q + 1) * self.H]
         return out
 
-    def run(self, gx, gxi, outi, out, out_dir_stride, B, col=0, out_cols=None):
+    def _state0(self, B, h0, c0):
+        """the state a recurrence starts from: zeros, or h0 bf16 / c0 f32 [ndir, Hp] broadcast over the batch
+        -> h bf16 [2, ndir, B, Hp] (h[0] = h_0), c f32 [ndir, B, Hp]"""
+        h = torch.zeros((2, self.ndir, B, self.Hp), dtype=BF16, device=self.device)
+        c = torch.zeros((self.ndir, B, self.Hp), dtype=F32, device=self.device)
+        if h0 is not None:
+            h[0] = h0.view(self.ndir, 1, self.Hp)
+        if c0 is not None:
+            c += c0.view(self.ndir, 1, self.Hp)
+        return h, c
+
+    def run(self, gx, gxi, outi, out, out_dir_stride, B, col=0, out_cols=None, h0=None, c0=None):
         """gx bf16 [rows, ndir*4Hp]; gxi / outi int32 [steps, ndir, B] (device); out bf16 [rows_out, ld]; col: first column of
         direction 0's h inside `out`, direction d at col + d * out_dir_stride -- or out_cols: one first column per direction.
+        h0 bf16 / c0 f32 [ndir, Hp]: the initial state of every sequence (default zeros).
         The whole recurrence is ONE call into the library (kbner_lstm_seq: one launch per time step, enqueued back to back)."""
         steps = gxi.shape[0]
         if out_cols is None:
             out_cols = [col + d * out_dir_stride for d in range(self.ndir)]
         if len(out_cols) != self.ndir or any(int(x) % 4 for x in out_cols):
             raise L_.KbnerError("LSTM output column offsets: one per direction, each a multiple of 4")
-        h = torch.zeros((2, self.ndir, B, self.Hp), dtype=BF16, device=self.device)
-        c = torch.zeros((self.ndir, B, self.Hp), dtype=F32, device=self.device)
+        h, c = self._state0(B, h0, c0)
         oc = torch.tensor([int(x) for x in out_cols], dtype=I32, device=self.device)
         gxi, outi = gxi.contiguous(), outi.contiguous()
         L_.call("kbner_lstm_seq", L_.ptr(gx), gx.shape[-1], L_.ptr(gxi), L_.ptr(self.whh), L_.ptr(h), L_.ptr(c), L_.ptr(out),
@@ -75,19 +87,20 @@ class LSTMGroup:
         """Whh of every direction transposed, bf16 [ndir, Hp, 4Hp]: what kbner_lstm_seq_bwd reads (made once per optimizer step)"""
         return self.whh.transpose(1, 2).contiguous()
 
-    def run_train(self, gx, gxi_host, out, B, out_cols):
-        """The recurrence from h_0 = c_0 = 0 through kbner_lstm_seq_train.  gxi_host int32 [steps, ndir, B] (numpy; used as outi
-        too), checked against the training contract before upload.  -> the saved state for run_bwd."""
+    def run_train(self, gx, gxi_host, out, B, out_cols, h0=None, c0=None):
+        """The recurrence from h_0 = c_0 = 0 (or h0 bf16 / c0 f32 [ndir, Hp], broadcast over the batch) through
+        kbner_lstm_seq_train.  gxi_host int32 [steps, ndir, B] (numpy; used as outi too), checked against the training contract
+        before upload.  -> the saved state for run_bwd."""
         gxi_host = check_prefix_active(gxi_host, gx.shape[0], self.ndir, B)
         if len(out_cols) != self.ndir or any(int(x) % 4 for x in out_cols):
             raise L_.KbnerError("LSTM output column offsets: one per direction, each a multiple of 4")
         steps, rows, Hp, nd = gxi_host.shape[0], gx.shape[0], self.Hp, self.ndir
         tab = torch.from_numpy(gxi_host).to(self.device)
-        h = torch.zeros((2, nd, B, Hp), dtype=BF16, device=self.device)
-        c = torch.zeros((nd, B, Hp), dtype=F32, device=self.device)
+        h, c = self._state0(B, h0, c0)
         oc = torch.tensor([int(x) for x in out_cols], dtype=I32, device=self.device)
         # zero-filled: the weight-gradient GEMMs read every row, consumed or not
-        saved = dict(gates=torch.zeros((rows, nd * 4 * Hp), dtype=BF16, device=self.device),
+        saved = dict(c0=None if c0 is None else c.clone(),      # (the kernel advances c in place)
+                     gates=torch.zeros((rows, nd * 4 * Hp), dtype=BF16, device=self.device),
                      cs=torch.zeros((rows, nd * Hp), dtype=F32, device=self.device),
                      hprev=torch.zeros((rows, nd * Hp), dtype=BF16, device=self.device), tab=tab, oc=oc, steps=steps, B=B)
         L_.call("kbner_lstm_seq_train", L_.ptr(gx), gx.shape[-1], L_.ptr(tab), L_.ptr(self.whh), L_.ptr(h), L_.ptr(c), L_.ptr(out),
@@ -95,11 +108,19 @@ class LSTMGroup:
                 L_.ptr(saved["hprev"]), L_.stream_ptr())
         return saved
 
-    def run_bwd(self, dout, saved, whh_t):
-        """dout bf16 [rows_out, ld]: the gradient of run_train's `out` -> dgx bf16 [rows, ndir*4Hp] (zero where nothing was consumed)"""
+    def run_bwd(self, dout, saved, whh_t, state_grads=False):
+        """dout bf16 [rows_out, ld]: the gradient of run_train's `out` -> dgx bf16 [rows, ndir*4Hp] (zero where nothing was consumed).
+        state_grads: through kbner_lstm_seq_bwd_init, which reads the c_0 run_train started from
+        -> (dgx, d c_0 f32 [ndir, B, Hp], d h_0 f32 [ndir, B, Hp])"""
         rows, Hp, nd, B = saved["gates"].shape[0], self.Hp, self.ndir, saved["B"]
         dgx = torch.zeros((rows, nd * 4 * Hp), dtype=BF16, device=self.device)
         carry = torch.zeros((nd, B, Hp), dtype=F32, device=self.device)
+        if state_grads:
+            dh0 = torch.zeros((nd, B, Hp), dtype=F32, device=self.device)
+            L_.call("kbner_lstm_seq_bwd_init", L_.ptr(dout), dout.shape[-1], L_.ptr(saved["oc"]), L_.ptr(saved["tab"]),
+                    L_.ptr(saved["tab"]), L_.ptr(whh_t), L_.ptr(saved["gates"]), L_.ptr(saved["cs"]), L_.ptr(saved["c0"]), L_.ptr(carry),
+                    L_.ptr(dgx), dgx.shape[-1], L_.ptr(dh0), saved["steps"], B, Hp, nd, L_.stream_ptr())
+            return dgx, carry, dh0
         L_.call("kbner_lstm_seq_bwd", L_.ptr(dout), dout.shape[-1], L_.ptr(saved["oc"]), L_.ptr(saved["tab"]), L_.ptr(saved["tab"]),
                 L_.ptr(whh_t), L_.ptr(saved["gates"]), L_.ptr(saved["cs"]), L_.ptr(carry), L_.ptr(dgx), dgx.shape[-1], saved["steps"], B,
                 Hp, nd, L_.stream_ptr())
@@ -159,11 +180,149 @@ def check_prefix_active(gxi, rows, ndir, B):
     return np.ascontiguousarray(t, np.int32)
 
 
-class BiLSTMHead:
-    """BiLSTM(D -> hidden, 1 layer) + linear(2*hidden -> T) on the concatenated features (sequence_tagger_model.py:969-1027)."""
+class _Block:
+    """A parameter block beside the head's one-layer arena: a flat fp32 arena of `_FIELDS` (each padded to 4 floats), a gradient
+    buffer once training is enabled, and a bf16 shadow of the first `n_shadow` floats (the GEMM / recurrence operands)."""
+    _FIELDS = ()
 
-    def __init__(self, rnn_state, linear_w, linear_b, blocks, hidden, device, transitions=None, trainable=False):
-        """rnn_state: torch.nn.LSTM state dict (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0 and *_reverse);
+    def _alloc(self, shapes, n_shadow_before, device):
+        self.device = torch.device(device)
+        self.shapes, self.offsets, off = shapes, {}, 0
+        for k in self._FIELDS:
+            self.offsets[k] = off
+            off += _round_up(int(np.prod(shapes[k])), 4)
+        self.n = off
+        self.n_shadow = self.offsets[n_shadow_before] if n_shadow_before else 0
+        self.arena = torch.zeros(self.n, dtype=F32, device=self.device)
+        self.shadow = torch.zeros(self.n_shadow, dtype=BF16, device=self.device) if self.n_shadow else None
+        self.g = None
+
+    def enable_training(self):
+        if self.g is None:
+            self.g = torch.zeros(self.n, dtype=F32, device=self.device)
+
+    def param(self, name, buf=None):
+        buf = self.arena if buf is None else buf
+        o, shp = self.offsets[name], self.shapes[name]
+        return buf[o:o + int(np.prod(shp))].view(shp)
+
+    def grad(self, name):
+        return self.param(name, self.g)
+
+
+class UpperLayer(_Block):
+    """Layer k >= 1 of the head's BiLSTM (torch.nn.LSTM(num_layers > 1): it reads the two-direction output of layer k - 1):
+    [ Wih [8Hp, 2Hp] | Whh [2, 4Hp, Hp] | bias_ih [8Hp] | bias_hh [8Hp] ], shadow: Wih, Whh.  Wih's 2H input columns sit at [0, H) and
+    [Hp, Hp + H) -- where the recurrence writes the two directions, the placement linear.weight uses.  All at lr * lr_rate."""
+    _FIELDS = ("wih", "whh", "bias_ih", "bias_hh")
+    _KEYS = ("weight_ih_l%d", "weight_hh_l%d", "bias_ih_l%d", "bias_hh_l%d")
+
+    def __init__(self, k, rnn_state, hidden, Hp, device):
+        self.k, self.H, self.Hp = int(k), int(hidden), int(Hp)
+        self._alloc({"wih": (8 * Hp, 2 * Hp), "whh": (2, 4 * Hp, Hp), "bias_ih": (8 * Hp,), "bias_hh": (8 * Hp,)}, "bias_ih", device)
+        self.grp = LSTMGroup.__new__(LSTMGroup)
+        self.grp.H, self.grp.Hp, self.grp.ndir, self.grp.device = self.H, self.Hp, 2, self.device
+        self.load_state(rnn_state)
+
+    def keys(self, sfx=""):
+        return [key % self.k + sfx for key in self._KEYS]
+
+    def load_state(self, rnn):
+        H, Hp = self.H, self.Hp
+        pad = self.grp.pad_gates
+        self.arena.zero_()
+        wih, whh = torch.zeros(self.shapes["wih"], dtype=F32), torch.zeros(self.shapes["whh"], dtype=F32)
+        bih, bhh = torch.zeros(8 * Hp, dtype=F32), torch.zeros(8 * Hp, dtype=F32)
+        for d, sfx in enumerate(("", "_reverse")):
+            kw, kh, kbi, kbh = self.keys(sfx)
+            w = pad(rnn[kw])
+            if tuple(w.shape) != (4 * Hp, 2 * H):
+                raise ValueError("%s is %s, layer %d of a %d-unit BiLSTM reads [%d, %d]" % (kw, tuple(rnn[kw].shape), self.k, H, 4 * H, 2 * H))
+            blk = slice(d * 4 * Hp, (d + 1) * 4 * Hp)
+            wih[blk, :H], wih[blk, Hp:Hp + H] = w[:, :H], w[:, H:]
+            whh[d, :, :H] = pad(rnn[kh])
+            bih[blk], bhh[blk] = pad(rnn[kbi]), pad(rnn[kbh])
+        for name, v in (("wih", wih), ("whh", whh), ("bias_ih", bih), ("bias_hh", bhh)):
+            self.param(name).copy_(v.to(self.device))
+        self.shadow.copy_(self.arena[:self.n_shadow])
+        if self.g is not None:
+            self.g.zero_()
+        self._refresh()
+
+    def state(self, buf=None):
+        """the block (or a buffer laid out like it) under torch.nn.LSTM's names for layer k (host float32)"""
+        H, Hp = self.H, self.Hp
+        unpad = lambda t: torch.cat([t[q * Hp:q * Hp + H] for q in range(4)], 0)   # noqa: E731
+        p = {name: self.param(name, buf).detach().cpu() for name in self._FIELDS}
+        out = {}
+        for d, sfx in enumerate(("", "_reverse")):
+            kw, kh, kbi, kbh = self.keys(sfx)
+            blk = slice(d * 4 * Hp, (d + 1) * 4 * Hp)
+            w = unpad(p["wih"][blk])
+            out[kw] = torch.cat([w[:, :H], w[:, Hp:Hp + H]], 1).contiguous()
+            out[kh] = unpad(p["whh"][d])[:, :H].contiguous()
+            out[kbi], out[kbh] = unpad(p["bias_ih"][blk]).contiguous(), unpad(p["bias_hh"][blk]).contiguous()
+        return out
+
+    def _refresh(self):
+        Hp = self.Hp
+        self.wih = self.shadow[:8 * Hp * 2 * Hp].view(8 * Hp, 2 * Hp)
+        self.grp.whh = self.shadow[self.offsets["whh"]:self.n_shadow].view(2, 4 * Hp, Hp)
+        self.bias = self.param("bias_ih") + self.param("bias_hh")
+        self._whht = None
+
+
+class InitState(_Block):
+    """The trained initial state of the head's BiLSTM (train_initial_hidden_state: lstm_init_h / lstm_init_c, [2L, H] in torch's
+    (layer, direction) order, row 2k + d; sequence_tagger_model.py:346-357): [ h [2L, Hp] | c [2L, Hp] ] in fp32, no shadow -- the
+    recurrence starts from bf16(h) (its state type) and the fp32 c.  At lr * lr_rate."""
+    _FIELDS = ("h", "c")
+
+    def __init__(self, state, layers, hidden, Hp, device):
+        self.L, self.H, self.Hp = int(layers), int(hidden), int(Hp)
+        self._alloc({"h": (2 * self.L, Hp), "c": (2 * self.L, Hp)}, None, device)
+        self.load_state(state)
+
+    def load_state(self, state):
+        self.arena.zero_()
+        for name in self._FIELDS:
+            v = torch.as_tensor(state["lstm_init_" + name]).detach().float().cpu()
+            if tuple(v.shape) != (2 * self.L, self.H):
+                raise ValueError("lstm_init_%s is %s, a %d-layer BiLSTM of %d units has [%d, %d]"
+                                 % (name, tuple(v.shape), self.L, self.H, 2 * self.L, self.H))
+            self.param(name)[:, :self.H] = v.to(self.device)
+        if self.g is not None:
+            self.g.zero_()
+        self._refresh()
+
+    def state(self, buf=None):
+        return {"lstm_init_" + name: self.param(name, buf)[:, :self.H].detach().cpu().contiguous() for name in self._FIELDS}
+
+    def _refresh(self):
+        self.h16 = self.param("h").to(BF16)
+
+    def of_layer(self, k):
+        """-> (h_0 bf16 [2, Hp], c_0 f32 [2, Hp]) of layer k"""
+        return self.h16[2 * k:2 * k + 2], self.param("c")[2 * k:2 * k + 2]
+
+
+def rnn_layer_count(rnn_state):
+    """the number of layers a torch.nn.LSTM state dict holds"""
+    k = 0
+    while "weight_ih_l%d" % k in rnn_state:
+        k += 1
+    return k
+
+
+class BiLSTMHead:
+    """BiLSTM(D -> hidden, L layers) + linear(2*hidden -> T) on the concatenated features (sequence_tagger_model.py:317-357,969-1027).
+    Layer 0 and the linear / CRF parameters are the one-layer head's arena, unchanged; every layer above it (UpperLayer) and the
+    trained initial state (InitState) are parameter blocks of their own beside it."""
+
+    def __init__(self, rnn_state, linear_w, linear_b, blocks, hidden, device, transitions=None, trainable=False, rnn_layers=1,
+                 init_state=None):
+        """rnn_state: torch.nn.LSTM state dict (weight_ih_l{k}, weight_hh_l{k}, bias_ih_l{k}, bias_hh_l{k} and *_reverse, k < rnn_layers);
+        init_state: None (the recurrences start from zeros) or {"lstm_init_h", "lstm_init_c"}, each [2 * rnn_layers, hidden];
         trainable (off by default: nothing more is allocated): enable_training() on this state and `transitions`;
         blocks: the widths D_i of the concatenated feature blocks in the reference's order (sorted embedding names).  Inside X
         every block starts at a multiple of 32 columns (`self.cols[i]`), so a producer whose width is padded (a 1000-unit LM
@@ -201,6 +360,14 @@ class BiLSTMHead:
         self.T = T
         self.arena = None
         self.training = False
+        self.L = int(rnn_layers)
+        if self.L < 1:
+            raise ValueError("rnn_layers must be at least 1 (got %r)" % (rnn_layers,))
+        if rnn_layer_count(rnn_state) != self.L:
+            raise ValueError("the BiLSTM state holds %d layer(s), this head has rnn_layers=%d" % (rnn_layer_count(rnn_state), self.L))
+        self.upper = [UpperLayer(k, rnn_state, self.H, Hp, self.device) for k in range(1, self.L)]
+        self.init = None if init_state is None else InitState(init_state, self.L, self.H, Hp, self.device)
+        self.rnn_dropout = 0.5 if self.L > 1 else 0.0      # torch.nn.LSTM(dropout=...) as the reference hard-codes it (:341-344)
         if trainable:
             self.enable_training(rnn_state, linear_w, linear_b, transitions)
 
@@ -219,9 +386,24 @@ class BiLSTMHead:
             ops.gemm(GEMM_NT, X, self.wih, Mp, 8 * Hp, self.Dp, C=gx, bias=self.bias, epi=EPI_BIAS)
             tab = torch.from_numpy(step_tables(lengths, n)).to(self.device)
             out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=self.device)
-            self.grp.run(gx, tab, tab, out, Hp, B)
+            h0, c0 = self._init_of(0)
+            self.grp.run(gx, tab, tab, out, Hp, B, h0=h0, c0=c0)
+            for lay in self.upper:      # (no dropout between the layers outside training)
+                gx = torch.empty((Mp, 8 * Hp), dtype=BF16, device=self.device)
+                ops.gemm(GEMM_NT, out, lay.wih, Mp, 8 * Hp, 2 * Hp, C=gx, bias=lay.bias, epi=EPI_BIAS)
+                out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=self.device)
+                h0, c0 = self._init_of(lay.k)
+                lay.grp.run(gx, tab, tab, out, Hp, B, h0=h0, c0=c0)
             em = ops.head_fwd(out[:B * n], self.lin_w, self.lin_b)
         return em.view(B, n, self.T)
+
+    def _init_of(self, k):
+        """(h_0 bf16, c_0 f32), each [2, Hp], of layer k -- (None, None) without a trained initial state: zeros"""
+        return (None, None) if self.init is None else self.init.of_layer(k)
+
+    def blocks_extra(self):
+        """the parameter blocks beside the one-layer arena, in the order the optimizer steps them: upper layers, initial state"""
+        return list(self.upper) + ([self.init] if self.init is not None else [])
 
 
     # ------------------------------------------------------------------ training (opt-in)
@@ -255,7 +437,10 @@ class BiLSTMHead:
         self.dropout = self.word_dropout = self.locked_dropout = 0.0
         self._drop_rng = np.random.default_rng(0)
         self.last_drop = None
-        self.load_state({"rnn": rnn_state, "linear.weight": linear_w, "linear.bias": linear_b, "transitions": transitions})
+        for blk in self.blocks_extra():     # (a one-layer head without an initial state has none)
+            blk.enable_training()
+        self.load_state({"rnn": rnn_state, "linear.weight": linear_w, "linear.bias": linear_b, "transitions": transitions},
+                        _extra=False)
 
     def param(self, name, buf=None):
         buf = self.arena if buf is None else buf
@@ -265,10 +450,21 @@ class BiLSTMHead:
     def grad(self, name):
         return self.param(name, self.g)
 
-    def load_state(self, state):
-        """the reference-layout dict load_stack_state takes -> the arena (padded layouts); the inverse of state()"""
+    def load_state(self, state, _extra=True):
+        """the reference-layout dict load_stack_state takes -> the arena (padded layouts) and, of a deeper head or one with a trained
+        initial state, the blocks beside it; the inverse of state()"""
         Hp, H, T = self.Hp, self.H, self.T
         rnn = state["rnn"]
+        if rnn_layer_count(rnn) != self.L:
+            raise ValueError("the state holds a BiLSTM of %d layer(s), this head has rnn_layers=%d" % (rnn_layer_count(rnn), self.L))
+        if _extra:
+            if ("lstm_init_h" in state) != (self.init is not None):
+                raise ValueError("the state %s a trained initial state (lstm_init_h / lstm_init_c), this head %s"
+                                 % (("carries", "has none") if "lstm_init_h" in state else ("carries no", "has one")))
+            for lay in self.upper:
+                lay.load_state(rnn)
+            if self.init is not None:
+                self.init.load_state(state)
         self.arena.zero_()
         wih, whh = torch.zeros(self.shapes["wih"], dtype=F32), torch.zeros(self.shapes["whh"], dtype=F32)
         bih, bhh = torch.zeros(8 * Hp, dtype=F32), torch.zeros(8 * Hp, dtype=F32)
@@ -306,12 +502,32 @@ class BiLSTMHead:
             rnn["bias_ih_l0" + sfx] = unpad(p["bias_ih"][d * 4 * Hp:(d + 1) * 4 * Hp]).contiguous()
             rnn["bias_hh_l0" + sfx] = unpad(p["bias_hh"][d * 4 * Hp:(d + 1) * 4 * Hp]).contiguous()
         lw = p["linear.weight"]
-        return {"rnn": rnn, "linear.weight": torch.cat([lw[:, :H], lw[:, Hp:Hp + H]], 1).contiguous(),
-                "linear.bias": p["linear.bias"].clone(), "transitions": p["transitions"].clone()}
+        out = {"rnn": rnn, "linear.weight": torch.cat([lw[:, :H], lw[:, Hp:Hp + H]], 1).contiguous(),
+               "linear.bias": p["linear.bias"].clone(), "transitions": p["transitions"].clone()}
+        if buf is None:     # (a buffer is laid out like the one-layer arena: the blocks beside it have buffers of their own)
+            for lay in self.upper:
+                rnn.update(lay.state())
+            if self.init is not None:
+                out.update(self.init.state())
+        return out
 
     def state_of(self, buf):
         """a buffer laid out like the arena (the gradient, an optimizer moment) in the reference's layout"""
         return self.state(buf)
+
+    def grad_state(self):
+        """every gradient in the reference's layout: state_of(g) with the upper layers' and the initial state's"""
+        out = self.state(self.g)
+        for lay in self.upper:
+            out["rnn"].update(lay.state(lay.g))
+        if self.init is not None:
+            out.update(self.init.state(self.init.g))
+        return out
+
+    def zero_grad(self):
+        self.g.zero_()
+        for blk in self.blocks_extra():
+            blk.g.zero_()
 
     def _refresh(self):
         """after the arena changed (optimizer step, load_state): what emissions() and loss_backward() read"""
@@ -323,6 +539,8 @@ class BiLSTMHead:
         self.bias = self.param("bias_ih") + self.param("bias_hh")
         self.lin_w, self.lin_b = self.param("linear.weight"), self.param("linear.bias")
         self._whht = None
+        for blk in self.blocks_extra():
+            blk._refresh()
 
     def seed_dropout(self, seed):
         self._drop_rng = np.random.default_rng(int(seed))
@@ -333,13 +551,19 @@ class BiLSTMHead:
 
     def _draw_dropout(self, n):
         """one training forward's dropout sites, drawn from the head's counter-based stream: (word-dropped positions bool [n] or
-        None, pre-RNN (element, locked) sites, post-RNN (element, locked) sites), each site a (seed, thresh) pair"""
-        if not self.training or not (self.dropout or self.word_dropout or self.locked_dropout):
+        None, pre-RNN (element, locked) sites, post-RNN (element, locked) sites), each site a (seed, thresh) pair.  A head of L > 1
+        layers draws, after these, the L - 1 element sites between its layers (rate rnn_dropout) as a fourth item -- also when the
+        three rates above are 0; a one-layer head draws exactly what it always drew."""
+        if not self.training or not (self.dropout or self.word_dropout or self.locked_dropout or self.L > 1):
             return None
         word = (self._drop_rng.random(n) < self.word_dropout) if self.word_dropout > 0.0 else None
         sd = self._drop_rng.integers(0, 2 ** 32, size=4, dtype="uint64")
         te, tl = ops.drop_thresh(self.dropout), ops.drop_thresh(self.locked_dropout)
-        return word, ((int(sd[0]), te), (int(sd[1]), tl)), ((int(sd[2]), te), (int(sd[3]), tl))
+        sites = word, ((int(sd[0]), te), (int(sd[1]), tl)), ((int(sd[2]), te), (int(sd[3]), tl))
+        if self.L > 1:
+            si = self._drop_rng.integers(0, 2 ** 32, size=self.L - 1, dtype="uint64")
+            sites += (tuple((int(x), ops.drop_thresh(self.rnn_dropout)) for x in si),)
+        return sites
 
     def loss_backward(self, X, lengths, B, n, batch, start, stop, loss_scale=1.0, weights=None, drop="draw", source=None, char=None):
         """One micro-batch of head training on constant features: forward, CRF NLL, and loss_scale * its gradient ADDED to self.g.
@@ -361,8 +585,10 @@ class BiLSTMHead:
             sites = self._draw_dropout(n) if drop == "draw" else drop
             self.last_drop = sites
             ident = None
+            inter = None       # the element sites between the layers (a fourth item of `sites`: heads of more than one layer)
             if sites is not None:
-                word, pre, post = sites
+                word, pre, post = sites[:3]
+                inter = sites[3] if len(sites) > 3 else None
                 ident = torch.arange(R, dtype=I32, device=dev)
             if source is not None:
                 # the whole first stage as ONE launch from the stored rows: Xt [Mp, Dq] written whole (padding rows and columns too)
@@ -387,7 +613,21 @@ class BiLSTMHead:
             gx = torch.empty((Mp, 8 * Hp), dtype=BF16, device=dev)
             ops.gemm(GEMM_NT, Xt, self.wih_t, Mp, 8 * Hp, self.Dq, C=gx, bias=self.bias, epi=EPI_BIAS)
             out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
-            saved = self.grp.run_train(gx, step_tables(lengths, n), out, B, [0, Hp])
+            deep = self.L > 1 or self.init is not None      # (a one-layer head from zeros launches what it always launched)
+            h0, c0 = self._init_of(0)
+            saved = self.grp.run_train(gx, step_tables(lengths, n), out, B, [0, Hp], h0=h0, c0=c0)
+            upper = []         # per upper layer: (layer, the matrix its input GEMM read, what its recurrence saved, its site)
+            for lay in self.upper:
+                site = inter[lay.k - 1] if inter is not None else ops.NO_DROP
+                inp = out
+                if site[1]:    # torch.nn.LSTM's dropout on the output of every layer but the last: element site only
+                    inp = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
+                    ops.gather_rows_drop(out, ident, n, site, ops.NO_DROP, out=inp)
+                gxk = torch.empty((Mp, 8 * Hp), dtype=BF16, device=dev)
+                ops.gemm(GEMM_NT, inp, lay.wih, Mp, 8 * Hp, 2 * Hp, C=gxk, bias=lay.bias, epi=EPI_BIAS)
+                out = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
+                h0, c0 = self._init_of(lay.k)
+                upper.append((lay, inp, lay.grp.run_train(gxk, step_tables(lengths, n), out, B, [0, Hp], h0=h0, c0=c0), site))
             post_on = sites is not None and bool(post[0][1] or post[1][1])
             feat = ops.gather_rows_drop(out, ident, n, post[0], post[1]) if post_on else out[:R]
             em = ops.head_fwd(feat, self.lin_w, self.lin_b)
@@ -415,25 +655,23 @@ class BiLSTMHead:
                 ops.scatter_rows_drop(dfeat, ident, dout, n, post[0], post[1])
             else:
                 dout = dfeat
+            # the layers above the first, last one first: each hands the gradient of its input to the layer below
+            for lay, inp, sv, site in reversed(upper):
+                if lay._whht is None:
+                    lay._whht = lay.grp.whh_t()
+                dgxk = self._recurrence_bwd(lay.grp, lay.k, dout, sv, lay._whht, True)
+                self._weight_grads(dgxk, inp, 2 * Hp, sv["hprev"], Mp, lay.grad)
+                dinp = torch.empty((Mp, 2 * Hp), dtype=BF16, device=dev)
+                ops.gemm(GEMM_NN, dgxk, lay.wih, Mp, 2 * Hp, 8 * Hp, C=dinp)
+                if site[1]:
+                    dout = torch.zeros((Mp, 2 * Hp), dtype=BF16, device=dev)
+                    ops.scatter_rows_drop(dinp, ident, dout, n, site, ops.NO_DROP)
+                else:
+                    dout = dinp
             if self._whht is None:
                 self._whht = self.grp.whh_t()
-            dgx = self.grp.run_bwd(dout, saved, self._whht)
-            # weight gradients: fp32 atomic accumulation on the 128x128 kernel (lda given: it takes N in multiples of 128), the row
-            # (reduction) dimension split until the launch has enough workgroups
-            sk = 1
-            while (8 * Hp // 128) * (self.Dq // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
-                sk *= 2
-            ops.gemm(GEMM_TN, dgx, Xt, 8 * Hp, self.Dq, Mp, C32=self.grad("wih"), epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
-            cross = torch.zeros((8 * Hp, 2 * Hp), dtype=F32, device=dev)
-            sk = 1
-            while (8 * Hp // 128) * (2 * Hp // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
-                sk *= 2
-            ops.gemm(GEMM_TN, dgx, saved["hprev"], 8 * Hp, 2 * Hp, Mp, C32=cross, epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
-            gw = self.grad("whh")
-            gw[0] += cross[:4 * Hp, :Hp]
-            gw[1] += cross[4 * Hp:, Hp:]
-            ops.colsum(dgx, self.grad("bias_ih"))
-            ops.colsum(dgx, self.grad("bias_hh"))
+            dgx = self._recurrence_bwd(self.grp, 0, dout, saved, self._whht, deep)
+            self._weight_grads(dgx, Xt, self.Dq, saved["hprev"], Mp, self.grad)
             if char is not None:
                 # the one window of dXt = dgx . Wih anything reads: the character block's columns.  The GEMM takes N in multiples of
                 # 128, so the window is CHAR_WINDOW columns of wih_t (leading dimension Dq) that contain the block.
@@ -443,6 +681,39 @@ class BiLSTMHead:
                 ops.gemm(GEMM_NN, dgx, self.wih_t.reshape(-1)[c0:], Mp, CHAR_WINDOW, 8 * Hp, C=dwin, lda=8 * Hp, ldb=self.Dq)
                 char.backward(dwin, char.col - c0, n)
         return loss[0]
+
+    def _recurrence_bwd(self, grp, k, dout, saved, whh_t, deep):
+        """layer k's walk back through time -> dgx.  deep: through kbner_lstm_seq_bwd_init; with a trained initial state the
+        gradients of c_0 and h_0, summed over the batch, are added to rows 2k, 2k + 1 of its gradient"""
+        if not deep:
+            return grp.run_bwd(dout, saved, whh_t)
+        dgx, dc0, dh0 = grp.run_bwd(dout, saved, whh_t, state_grads=True)
+        if self.init is not None:
+            B = saved["B"]
+            for d in range(2):
+                ops.colsum_rows_f32(dc0[d], B, self.init.grad("c")[2 * k + d])
+                ops.colsum_rows_f32(dh0[d], B, self.init.grad("h")[2 * k + d])
+        return dgx
+
+    def _weight_grads(self, dgx, inp, W, hprev, Mp, grad):
+        """one layer's dWih = dgx^T inp ([8Hp, W]), dWhh from dgx^T hprev and both bias gradients, ADDED to grad(name): fp32 atomic
+        accumulation on the 128x128 kernel (lda given: it takes N in multiples of 128), the row (reduction) dimension split until
+        the launch has enough workgroups"""
+        Hp, dev = self.Hp, self.device
+        sk = 1
+        while (8 * Hp // 128) * (W // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
+            sk *= 2
+        ops.gemm(GEMM_TN, dgx, inp, 8 * Hp, W, Mp, C32=grad("wih"), epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
+        cross = torch.zeros((8 * Hp, 2 * Hp), dtype=F32, device=dev)
+        sk = 1
+        while (8 * Hp // 128) * (2 * Hp // 128) * sk < 768 and Mp % (128 * sk) == 0 and sk < 64:
+            sk *= 2
+        ops.gemm(GEMM_TN, dgx, hprev, 8 * Hp, 2 * Hp, Mp, C32=cross, epi=EPI_ATOMIC32, splitk=sk, lda=8 * Hp)
+        gw = grad("whh")
+        gw[0] += cross[:4 * Hp, :Hp]
+        gw[1] += cross[4 * Hp:, Hp:]
+        ops.colsum(dgx, grad("bias_ih"))
+        ops.colsum(dgx, grad("bias_hh"))
 
 
 CHAR_WINDOW = 128       # columns of the dXt window computed for the character block (the GEMM's N granule)
@@ -746,7 +1017,7 @@ class FeatureStore:
 
 
 class StackOptimizer:
-    """The optimizer of a trainable BiLSTMHead over its arena ranges: `linear.*` at lr, `rnn.*` and `transitions` at lr * lr_rate
+    """The optimizer of a trainable BiLSTMHead over its arena ranges: `linear.*` at lr, `rnn.*`, `lstm_init_*` and `transitions` at lr * lr_rate
     (the reference's two parameter groups, finetune_trainer.py:552-571), clip_grad_norm_(max_norm) from kbner_grad_sqnorm, then
     kbner_adamw_hf (HF AdamW: eps 1e-6, weight decay 0, bias correction) or kbner_sgd.  lr_scale multiplies both rates (the
     trainer's schedule)."""
@@ -774,6 +1045,9 @@ class StackOptimizer:
         out = [("rnn+transitions", h.split, self.lr * self.lr_rate * self.lr_scale), ("linear", h.n - h.split, self.lr * self.lr_scale)]
         if self.char is not None:
             out.append(("char", self.char.n, self.lr * self.lr_scale))
+        # rnn.*_l{k}, lstm_init_h and lstm_init_c: neither 'embedding' in the name nor linear.* (finetune_trainer.py:552-553)
+        for blk in h.blocks_extra():
+            out.append(("rnn layer %d" % blk.k if hasattr(blk, "k") else "lstm_init", blk.n, self.lr * self.lr_rate * self.lr_scale))
         return out
 
     def reset(self):
@@ -784,6 +1058,9 @@ class StackOptimizer:
         c = self.char
         self.cm = torch.zeros(c.n, dtype=F32, device=h.device) if (c is not None and self.name == "AdamW") else None
         self.cv = torch.zeros(c.n, dtype=F32, device=h.device) if (c is not None and self.name == "AdamW") else None
+        # one pair of moments per parameter block beside the arena (upper layers, initial state)
+        self.xm = [torch.zeros(b.n, dtype=F32, device=h.device) if self.name == "AdamW" else None for b in h.blocks_extra()]
+        self.xv = [torch.zeros(b.n, dtype=F32, device=h.device) if self.name == "AdamW" else None for b in h.blocks_extra()]
         self.t = 0
 
     def step(self, grad_scale=1.0):
@@ -794,6 +1071,9 @@ class StackOptimizer:
             c = self.char
             if c is not None:      # ONE clip norm over head and character gradients (clip_grad_norm_(model.parameters()))
                 ops.grad_sqnorm(c.g, self.ws, self.norm_sq, accumulate=True)
+            extra = h.blocks_extra()
+            for blk in extra:
+                ops.grad_sqnorm(blk.g, self.ws, self.norm_sq, accumulate=True)
             self.t += 1
             b1, b2 = self.betas
             bc = (1.0 - b2 ** self.t) ** 0.5 / (1.0 - b1 ** self.t)
@@ -814,6 +1094,13 @@ class StackOptimizer:
                               grad_scale, True)
                 else:
                     ops.sgd(c.arena, c.g, None, 0, lr, self.norm_sq, self.max_norm, grad_scale, True)
+            for blk, m, v in zip(extra, self.xm, self.xv):
+                lr = self.lr * self.lr_rate * self.lr_scale
+                if self.name == "AdamW":
+                    ops.adamw(blk.arena, blk.g, m, v, blk.shadow, blk.n_shadow, lr * bc, 0.0, b1, b2, self.eps, self.norm_sq,
+                              self.max_norm, grad_scale, True)
+                else:
+                    ops.sgd(blk.arena, blk.g, blk.shadow, blk.n_shadow, lr, self.norm_sq, self.max_norm, grad_scale, True)
             h._refresh()
         return self.norm_sq
 
